@@ -12,8 +12,14 @@ a satisfying random arithmetic circuit of the same size.  Prover-key
 evaluations = coset LDE of the coefficients; real coset points and Z_H
 values; SRS = [tau^i] G.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(with the rooflines and stage times read from the timed steps themselves).
+--dump-outputs DIR writes the last timed proof (the instance is seeded, so it
+is the same from run to run) as .npy arrays.  --full adds, after the timed
+steps, the check of the timed proof, the drop-in lines and the CPU baseline.
 
 N > 1: one process per GPU; all ranks prove the SAME instance together
 (DESIGN.md 6): every MSM is split by point ranges (rank r sums points
@@ -530,7 +536,7 @@ def op_traffic(path, key):
         return None
 
 
-def bench_ntt(ctx, lg: int, steps: int, warmup: int, verify: bool):
+def bench_ntt(ctx, lg: int, steps: int, warmup: int, verify: bool, dump: str = ""):
     """BASELINE config 2: natural-order radix-2 NTT / iNTT of 2^lg Montgomery
     Fr (pnp_ntt = the reference's Ntt / Intt, zksnark_ntt.cu:74-92 with
     arkworks semantics).  A batch of distinct vectors (>= 16 and >= 1 GiB in
@@ -567,6 +573,16 @@ def bench_ntt(ctx, lg: int, steps: int, warmup: int, verify: bool):
     ms, calls = ctx.kernel_stats("ntt")
     alg = ctx.kernel_bytes("ntt")
     ctx.kernel_timing(False)
+    if dump:
+        # the vectors as the last step left them; beyond DUMP_SAMPLE_ROWS
+        # elements a fixed (seeded) sample of them, in index order
+        flat = vecs.view(-1, 4)
+        rows = np.arange(flat.shape[0])
+        if rows.size > DUMP_SAMPLE_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(rows.size, DUMP_SAMPLE_ROWS, replace=False))
+        got = np.ascontiguousarray(flat[torch.from_numpy(rows).cuda()].cpu().numpy())
+        dump_outputs(dump, {"vectors": bytes_f32(got.tobytes()).reshape(-1, 32),
+                            "vector_rows": rows.astype(np.float64)})
     gbs = alg / (ms / 1e3) / 1e9
     per_call = ms / calls
     traffic = op_traffic(NTT_TRAFFIC_FILE, f"bytes_per_call_lg{lg}")
@@ -632,7 +648,7 @@ def bench_ntt(ctx, lg: int, steps: int, warmup: int, verify: bool):
     return out
 
 
-def bench_msm(ctx, lg: int, steps: int, warmup: int, verify: bool, world: int, rank: int):
+def bench_msm(ctx, lg: int, steps: int, warmup: int, verify: bool, world: int, rank: int, dump: str = ""):
     """BASELINE config 3: one 2^lg Pippenger MSM on BLS12-381 G1 against the
     resident commit key (pnp_commit_ck, the folded c = 20 layout gen_proof
     uses; sharded by bucket or point ranges when world > 1), points
@@ -671,6 +687,8 @@ def bench_msm(ctx, lg: int, steps: int, warmup: int, verify: bool, world: int, r
     acc_ms, acc_n = ctx.kernel_stats("msm_accumulate")
     madds = ctx.kernel_bytes("msm_madds")
     ctx.kernel_timing(False)
+    if dump and rank == 0:
+        dump_outputs(dump, {"commitment": bytes_f32(bytes(c.x) + bytes(c.y)).reshape(1, 96)})
     if world > 1:
         import torch.distributed as dist
         dev = "cuda" if os.environ.get("PNP_BENCH_BACKEND", "nccl") == "nccl" else "cpu"  # (gloo rehearsal)
@@ -720,6 +738,39 @@ def bench_msm(ctx, lg: int, steps: int, warmup: int, verify: bool, world: int, r
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 16
+
+
+def bytes_f32(raw):
+    """Exact integer data as float32: one value (0..255) per byte, little-endian
+    within each 64-bit limb as in memory."""
+    import numpy as np
+    return np.frombuffer(bytes(raw), dtype=np.uint8).astype(np.float32)
+
+
+def dump_outputs(d: str, arrays: dict):
+    """--dump-outputs: what the last timed step returned, DIR/<name>.npy each."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, over the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    log(f"outputs: {', '.join(f'{k}{list(v.shape)}' for k, v in arrays.items())} -> {d}")
+
+
+def proof_arrays(proof):
+    """A ProofC as its caller receives it: the 19 G1 commitments (x, y: 96
+    bytes each) and the 26 Fr evaluations (32 bytes each), Montgomery limbs."""
+    from pnp import abi
+    raw = abi.proof_to_bytes(proof)
+    split = 96 * len(abi.PROOF_COMMITMENTS)
+    return {"commitments": bytes_f32(raw[:split]).reshape(-1, 96),
+            "evaluations": bytes_f32(raw[split:]).reshape(-1, 32)}
+
+
 def relaunch(n: int) -> int:
     """Start N ranks (one per GPU) under torch.distributed.run as a CHILD
     process; this process never initialises the GPU (device_count() does not
@@ -749,20 +800,35 @@ def main():
     ap.add_argument("--circuit", default="merkle", choices=("merkle", "arith"),
                     help="merkle: the reference's Poseidon Merkle circuit (HEIGHT = lg - 7); "
                          "arith: a random satisfying arithmetic circuit of --gates gates")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the check of the "
+                         "timed proof (verifier, pairing, golden bytes), the drop-in lines (--drop-in, with "
+                         "the process-cold v1 calls first) and the CPU baseline (--cpu-lg); for --op ntt / "
+                         "msm the check against the CPU restatement and its timing.  Without it those "
+                         "three options have no effect")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, one value per "
+                         "byte): the proof's commitments and evaluations; --op msm: the commitment; "
+                         "--op ntt: a fixed sample of the transformed vectors")
     ap.add_argument("--cpu-lg", type=int, default=22,
-                    help="CPU baseline size (default: the bench's own HEIGHT=15 instance, ~150 s on 16 "
-                         "host threads); 0 = skip")
-    ap.add_argument("--no-verify", action="store_true", help="skip the proof check after the timed region")
+                    help="with --full: CPU baseline size (default: the bench's own HEIGHT=15 instance, "
+                         "~150 s on 16 host threads); 0 = skip")
+    ap.add_argument("--no-verify", action="store_true",
+                    help="with --full: skip the proof check after the timed region")
     ap.add_argument("--solo", default="", metavar="R/W",
                     help="time rank R's share of a W-GPU proof alone on this GPU (loopback exchanges, "
                          "proof discarded): the per-rank critical path of the multi-GPU bench")
     ap.add_argument("--stages", action="store_true", help="print per-stage ms to stderr")
     ap.add_argument("--drop-in", default="v1", choices=("", "v2", "v1"),
-                    help="also time the host-witness v2 call ('v2') and the v1 symbol ('v1')")
+                    help="with --full: also time the host-witness v2 call ('v2') and the v1 symbol ('v1')")
     ap.add_argument("--op", default="proof", choices=("proof", "ntt", "msm"),
                     help="proof: the headline gen_proof; ntt / msm: the operator lines of BASELINE configs "
                          "2 and 3 (python bench.py --op ntt --lg 20; --op msm --lg 22 [--gpus N])")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_verify, args.drop_in, args.cpu_lg = True, "", 0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return relaunch(args.gpus)
@@ -827,8 +893,9 @@ def main():
             log("bench: --op ntt runs on one GPU")
             return 2
         sys.path.insert(0, os.path.join(REPO, "tests"))
-        res = (bench_ntt(ctx, args.lg, args.steps, args.warmup, not args.no_verify) if args.op == "ntt" else
-               bench_msm(ctx, args.lg, args.steps, args.warmup, not args.no_verify, world, rank))
+        res = (bench_ntt(ctx, args.lg, args.steps, args.warmup, not args.no_verify, args.dump_outputs)
+               if args.op == "ntt" else
+               bench_msm(ctx, args.lg, args.steps, args.warmup, not args.no_verify, world, rank, args.dump_outputs))
         if rank == 0:
             print(json.dumps(res), flush=True)
         ctx.close()
@@ -907,6 +974,8 @@ def main():
         log(f"msm_accumulate: {acc_n} launches, {acc_ms / max(acc_n, 1):.3f} ms avg; "
             f"quotient: {q_n} launches, {q_ms / max(q_n, 1):.3f} ms avg")
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, proof_arrays(proof))
         acc_avg_s = acc_ms / max(acc_n, 1) / 1e3
         acc_s = acc_ms / 1e3
         # the dominant kernel's real work: mixed additions counted on the device

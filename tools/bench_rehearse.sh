@@ -8,5 +8,5 @@ set -o pipefail
 mkdir -p gpurun_out
 N=${1:-2}; LG=${2:-18}
 PNP_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --lg $LG --steps 2 --warmup 1 ${REHEARSE_ARGS:-} \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $N --lg $LG --steps 2 --warmup 1 ${REHEARSE_ARGS:-} \
   > gpurun_out/rehearse_n$N.json 2> gpurun_out/rehearse_n$N.err

@@ -9,8 +9,8 @@
 #
 #   tests[=K]        pytest -m gpu (optionally -k K, '+' for spaces), one process
 #   smoke            __graft_entry__.smoke()
-#   bench[=ARGS]     bench.py (default arguments unless ARGS, '+'-separated),
-#                    JSON line in bench.json, log in bench.err
+#   bench[=ARGS]     bench.py (--full with its default arguments unless ARGS,
+#                    '+'-separated), JSON line in bench.json, log in bench.err
 #   stats[=STEPS]    rocprofv3 --kernel-trace --stats over a short bench
 #   trace=ARGS       the same over bench.py ARGS ('+'-separated, e.g. --solo+7/8+--steps+2)
 #   pmc[=COUNTERS]   one rocprofv3 --pmc pass over one bench proof (counters
@@ -41,7 +41,8 @@ run_step() {
     bench*)
       # bench.json for the default arguments, bench_<args>.json otherwise
       local bn=bench${arg:+_$(echo "$arg" | tr -c 'A-Za-z0-9' '_' | cut -c1-40)}
-      timeout -k 10 900 python -u bench.py ${arg//+/ } > "$OUT/$bn.json" 2> "$OUT/$bn.err" ;;
+      local ba=${arg:---full}
+      timeout -k 10 900 python -u bench.py ${ba//+/ } > "$OUT/$bn.json" 2> "$OUT/$bn.err" ;;
     stats*)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/stats" -o run -- \
           python3 "$R/bench.py" --steps ${arg:-3} --warmup 1 --cpu-lg 0 --drop-in "" --no-verify > "$OUT/stats.log" 2>&1) ;;
@@ -68,7 +69,7 @@ run_step() {
       done ;;
     ab=*)
       local n=${arg%%:*} v=${arg#*:}
-      bash tools/abn.sh "$n" $(echo "$v" | tr ',' ' ') > "$OUT/ab.txt" 2>&1 ;;
+      ABN_OUT="$OUT/ab" bash tools/abn.sh "$n" $(echo "$v" | tr ',' ' ') > "$OUT/ab.txt" 2>&1 ;;
     rehearse=*)
       # bench.py's multi-rank path with N gloo ranks sharing the GPU (N:LG)
       local rn=${arg%%:*} rl=${arg#*:}
