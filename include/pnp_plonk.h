@@ -199,6 +199,18 @@ typedef struct {
  *                    fingerprint (field pointers, domain, 257 sampled words
  *                    per array) is unchanged: no upload.  Only for callers
  *                    that never mutate key contents in place.
+ *   PNP_V1_DERIVE=1  when the prover key has to be (re)loaded (decided as
+ *                    without the switch), load it through
+ *                    pnp_load_prover_key_coeffs: the 8n arrays are derived on
+ *                    the GPU instead of uploaded.  Only for callers whose
+ *                    *_evals are the coset FFTs of their *_coeffs and whose
+ *                    linear_evaluations / v_h_coset_8n are the standard
+ *                    coset's (any key built by the reference's preprocessing).
+ *                    Which optional selectors exist is read from their first D
+ *                    evaluations; the elements holding the 257 sampled words
+ *                    of every 8n array are compared with the derived values
+ *                    and a mismatch falls back to the full upload; an
+ *                    inconsistency in unsampled elements is not seen.
  *   PNP_V1_STRICT=1  exit with PNP_E_ENVELOPE for keys outside the reference
  *                    GPU path's circuit class (non-zero q_m / custom-gate /
  *                    q_lookup selectors or lookup tables): there this backend
@@ -243,6 +255,34 @@ int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t domain_size
                         int device_ptrs);
 int pnp_load_commit_key(pnp_ctx *ctx, const CommitKeyC *ck, uint64_t n_points,
                         int device_ptrs);
+
+/* The same resident key from its coefficient arrays alone.  A key built by the
+ * reference's preprocessing defines every 8n array as the coset FFT of a
+ * coefficient array of the same struct (preprocess.rs:174-255) or as a
+ * function of the domain size (linear_evaluations, v_h_coset_8n:
+ * preprocess.rs:257-264); this load derives them on the device, directly in
+ * the layout the prover reads, instead of copying 8n-sized arrays: at D = 2^22
+ * 2.1 GiB cross PCIe instead of 17.1 GiB, and with host pointers
+ * nothing 8n-sized stays resident beside the prover's own blocks.
+ * Afterwards the context is in the state pnp_load_prover_key leaves for the
+ * full key whose evaluations are consistent with these coefficients; the
+ * proofs are the same bytes.
+ *   read, D Fr each, must not be NULL (PNP_E_ARG, the field index in
+ *   pnp_last_error; the resident key is left as it was): the *_coeffs of q_l,
+ *   q_r, q_o, q_4, q_c, q_hl, q_hr, q_h4, q_arith and of the four sigmas,
+ *   and table1..4;
+ *   optional, the *_coeffs of q_m, range_selector, logic_selector,
+ *   fixed_group_add_selector, variable_group_add_selector, q_lookup: NULL is
+ *   the zero polynomial, anything else is D coefficients (an all-zero array
+ *   is treated exactly like NULL).  The v1 convention for a zero selector, an
+ *   empty Vec's dangling non-NULL pointer, cannot be told from an array here:
+ *   pass NULL;
+ *   never read, may be NULL: every *_evals, linear_evaluations, v_h_coset_8n.
+ * device_ptrs as for pnp_load_prover_key (the coefficient and table pointers
+ * are adopted in place).  With several ranks (pnp_set_exchange_a2a) only the
+ * rank's own coset blocks are derived. */
+int pnp_load_prover_key_coeffs(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t domain_size,
+                               int device_ptrs);
 
 /* The commit key straight from arkworks' memory, without the per-proof
  * conversion prove_pnp does today (prover.rs:700-711 rebuilds (x, y) tuples

@@ -1014,6 +1014,71 @@ bool host_all_zero(const uint64_t *p, uint64_t words) {
     return acc == 0;
 }
 
+
+// ---- steps shared by the two prover-key loads (pnp_load_prover_key: the
+// caller's 8n arrays re-laid into blocks; pnp_load_prover_key_coeffs: the
+// blocks derived from the coefficients) ----
+
+// The quotient's 8n arrays are kept in block layout (point 8j + m -> block m,
+// index j), only the blocks this rank owns: all 8 on one GPU; 8/world when the
+// round-4 pipeline is distributed (pnp_set_exchange_a2a)
+void pk_block_range(pnp_ctx *ctx) {
+    const int world = ctx->msm.world;
+    const bool split = world > 1 && 8 % world == 0 && ctx->msm.alltoall;
+    ctx->pk_nb = split ? 8 / world : 8;
+    ctx->pk_mb0 = split ? ctx->msm.rank * ctx->pk_nb : 0;
+}
+// k_quotient29's keys (protocol.h): no custom gate, no lookup selector or
+// table, the standard coset (the zero flags and pk_std_coset are set)
+bool pk_q29_class(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D) {
+    static const bool q29_on = [] {
+        const char *e = getenv("PNP_QUOT29");
+        return !e || atoi(e) != 0;
+    }();
+    bool q29 = q29_on && ctx->pk_std_coset && ctx->pk_qlookup_zero && !ctx->pk_custom_nz[0] &&
+               !ctx->pk_custom_nz[1] && !ctx->pk_custom_nz[2] && !ctx->pk_custom_nz[3];
+    const uint64_t *tabs[4] = {dev.table1, dev.table2, dev.table3, dev.table4};
+    for (int k = 0; k < 4 && q29; k++)
+        q29 = !tabs[k] || !pnp::k_any_nonzero(tabs[k], 4 * D, ctx->scratch_b, ctx->stream);
+    return q29;
+}
+// the block arrays a q29 key keeps in the 2^261 form (pk_blk29)
+bool pk_name_in29(const char *name) {
+    static const char *const names29[] = {"q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_hl", "q_hr",
+                                          "q_h4", "q_arith", "sig0", "sig1", "sig2", "sig3", "lin"};
+    for (const char *nm : names29)
+        if (strcmp(nm, name) == 0) return true;
+    return false;
+}
+// the sigma n-domain evaluations (gen_proof.cuh:159-165 recomputes
+// NTT.forward(sigma_coeffs) every proof)
+void pk_sigma_domain(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D, uint32_t lg) {
+    const uint64_t *sigc[4] = {dev.left_sigma_coeffs, dev.right_sigma_coeffs, dev.out_sigma_coeffs,
+                               dev.fourth_sigma_coeffs};
+    for (int j = 0; j < 4; j++) {
+        if (ctx->pk_sigma_n[j].bytes < 32 * D) ctx->pk_sigma_n[j].alloc(32 * D);
+        PNP_HIP(hipMemcpyAsync(ctx->pk_sigma_n[j].p, sigc[j], 32 * D, hipMemcpyDeviceToDevice, ctx->stream));
+        pnp::ntt_run(ctx->ntt, ctx->pk_sigma_n[j].u64(), lg, false, false, ctx->stream);
+    }
+}
+// drop the blocks of an earlier key this one does not have
+void pk_prune_blocks(std::map<std::string, pnp::DevBuf> &m, const std::vector<std::string> &u) {
+    for (auto it = m.begin(); it != m.end();)
+        it = std::find(u.begin(), u.end(), it->first) == u.end() ? m.erase(it) : std::next(it);
+}
+// the key is resident: what every load leaves behind
+void pk_load_done(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D) {
+    ctx->pk_blk_rank = ctx->msm.rank;
+    ctx->pk_blk_world = ctx->msm.world;
+    ctx->pk_pinv.release();
+    ctx->pk_pinv_pos = ~0ULL;
+    PNP_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->pk_dev = dev;
+    ctx->pk_n = D;
+    ctx->pk_loaded = true;
+    ctx->hbm_checked = false;  // the budget is checked by the next proof (pnp::hbm_budget)
+}
+
 }  // namespace
 
 extern "C" {
@@ -1079,16 +1144,9 @@ int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int devi
         ctx->pk_custom_nz[1] = dev.logic_selector_evals != nullptr;
         ctx->pk_custom_nz[2] = dev.fixed_group_add_selector_evals != nullptr;
         ctx->pk_custom_nz[3] = dev.variable_group_add_selector_evals != nullptr;
-        const uint64_t *sigc[4] = {dev.left_sigma_coeffs, dev.right_sigma_coeffs,
-                                   dev.out_sigma_coeffs, dev.fourth_sigma_coeffs};
         uint32_t lg = 0;
         while ((1ULL << lg) < D) lg++;
-        for (int j = 0; j < 4; j++) {
-            if (ctx->pk_sigma_n[j].bytes < 32 * D) ctx->pk_sigma_n[j].alloc(32 * D);
-            PNP_HIP(hipMemcpyAsync(ctx->pk_sigma_n[j].p, sigc[j], 32 * D, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-            pnp::ntt_run(ctx->ntt, ctx->pk_sigma_n[j].u64(), lg, false, false, ctx->stream);
-        }
+        pk_sigma_domain(ctx, dev, D, lg);
         // coset constants: v_h^-1 (the reference divides by v_h every proof,
         // quotient.cu:369-370); when the key's coset arrays are the standard
         // ones (x_i = 7 w_8n^i, v_h = x^n - 1, as every key built by the
@@ -1120,29 +1178,12 @@ int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int devi
             }
             PNP_HIP(hipStreamSynchronize(ctx->stream));
         }
-        // The quotient's 8n arrays in block layout (point 8j + m -> block m,
-        // index j), only the blocks this rank owns: all 8 on one GPU; 8/world
-        // when the round-4 pipeline is distributed (pnp_set_exchange_a2a)
-        const int world = ctx->msm.world;
-        const bool split = world > 1 && 8 % world == 0 && ctx->msm.alltoall;
-        ctx->pk_nb = split ? 8 / world : 8;
-        ctx->pk_mb0 = split ? ctx->msm.rank * ctx->pk_nb : 0;
-        // k_quotient29's keys (protocol.h): no custom gate, no lookup selector
-        // or table, the standard coset; their selector / sigma / lin blocks are
-        // kept in the 2^261 form (pk_blk29) and, but lin (the PI term), not in
-        // the 2^256 form at all
-        bool q29 = false;
-        {
-            static const bool q29_on = [] {
-                const char *e = getenv("PNP_QUOT29");
-                return !e || atoi(e) != 0;
-            }();
-            q29 = q29_on && ctx->pk_std_coset && ctx->pk_qlookup_zero && !ctx->pk_custom_nz[0] &&
-                  !ctx->pk_custom_nz[1] && !ctx->pk_custom_nz[2] && !ctx->pk_custom_nz[3];
-            const uint64_t *tabs[4] = {dev.table1, dev.table2, dev.table3, dev.table4};
-            for (int k = 0; k < 4 && q29; k++)
-                q29 = !tabs[k] || !pnp::k_any_nonzero(tabs[k], 4 * D, ctx->scratch_b, ctx->stream);
-        }
+        // the blocks this rank owns (pk_block_range)
+        pk_block_range(ctx);
+        // k_quotient29's keys (pk_q29_class): their selector / sigma / lin
+        // blocks are kept in the 2^261 form (pk_blk29) and, but lin (the PI
+        // term), not in the 2^256 form at all
+        const bool q29 = pk_q29_class(ctx, dev, D);
         std::vector<std::string> used, used29;
         const uint64_t blk_elems = (uint64_t)ctx->pk_nb * D;
         auto put = [&](std::map<std::string, pnp::DevBuf> &m, std::vector<std::string> &u, const char *name,
@@ -1154,10 +1195,7 @@ int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int devi
             u.push_back(name);
         };
         auto blk = [&](const char *name, const uint64_t *src) {
-            static const char *const names29[] = {"q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_hl", "q_hr",
-                                                  "q_h4", "q_arith", "sig0", "sig1", "sig2", "sig3", "lin"};
-            bool in29 = false;
-            for (const char *nm : names29) in29 |= strcmp(nm, name) == 0;
+            const bool in29 = pk_name_in29(name);
             if (q29 && in29) put(ctx->pk_blk29, used29, name, src, true);
             if (!(q29 && in29) || strcmp(name, "lin") == 0) put(ctx->pk_blk, used, name, src, false);
         };
@@ -1184,12 +1222,8 @@ int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int devi
         blk("vh_inv", vh_inv.u64());
         if (ctx->pk_std_coset) blk("l1v", l1v.u64());
         // blocks of an earlier key this one does not have
-        auto prune = [](std::map<std::string, pnp::DevBuf> &m, const std::vector<std::string> &u) {
-            for (auto it = m.begin(); it != m.end();)
-                it = std::find(u.begin(), u.end(), it->first) == u.end() ? m.erase(it) : std::next(it);
-        };
-        prune(ctx->pk_blk, used);
-        prune(ctx->pk_blk29, used29);
+        pk_prune_blocks(ctx->pk_blk, used);
+        pk_prune_blocks(ctx->pk_blk29, used29);
         ctx->pk_q29 = q29;
         // the coset-constant scratch (4 x 8n Fr) is kept only for callers that
         // load keys from host memory again and again (the v1 symbol); a
@@ -1199,15 +1233,126 @@ int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int devi
             PNP_HIP(hipStreamSynchronize(ctx->stream));
             for (auto &b : ctx->pk_tmp) b.release();
         }
-        ctx->pk_blk_rank = ctx->msm.rank;
-        ctx->pk_blk_world = world;
-        ctx->pk_pinv.release();
-        ctx->pk_pinv_pos = ~0ULL;
+        pk_load_done(ctx, dev, D);
+    });
+}
+
+// The same resident key from the coefficient arrays alone: every 8n array of
+// a key built by the reference's preprocessing is coset_fft of a coefficient
+// array the struct also carries (preprocess.rs:174-255) or a function of n
+// (linear_evaluations, v_h_coset_8n: preprocess.rs:257-264), so the blocks
+// pnp_load_prover_key copies out of the caller's arrays are derived here, by
+// the per-proof LDE (lde_blocks) and from closed forms (k_coset_blocks), and
+// nothing 8n-sized crosses PCIe or stays resident beside the blocks.
+int pnp_load_prover_key_coeffs(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int device_ptrs) {
+    if (!ctx || !pk || D == 0 || (D & (D - 1)) || D > (1ULL << 25)) return PNP_E_ARG;
+    uint64_t *const *src = reinterpret_cast<uint64_t *const *>(pk);
+    // the required fields are checked before anything is touched: a refused
+    // call leaves the resident key as it was
+    for (int f = 0; f < 44; f++)
+        if ((kPkKinds[f] == kCoeffs || kPkKinds[f] == kTable) && !src[f]) {
+            set_error("prover key field %d is null", f);
+            return PNP_E_ARG;
+        }
+    PNP_TRY({
+        tables_wait(ctx);  // a background build reads the key being replaced: let it finish
+        PNP_HIP(hipSetDevice(ctx->device));
+        ctx->pk_loaded = false;
+        ctx->pk_gen++;
+        ctx->pk_owned.resize(44);
+        ProverKeyC dev{};
+        uint64_t **dst = reinterpret_cast<uint64_t **>(&dev);
+        std::vector<H2D> up;
+        for (int f = 0; f < 44; f++) {
+            const FieldKind k = kPkKinds[f];
+            dst[f] = nullptr;
+            // never read: the evaluations; an optional selector without
+            // coefficients is the zero polynomial
+            if (k == kSkip || k == kEvals8 || k == kSelEvals8 || (k == kSelCoeffs && !src[f])) {
+                ctx->pk_owned[f].release();
+                continue;
+            }
+            if (device_ptrs) {
+                ctx->pk_owned[f].release();
+                dst[f] = src[f];
+            } else {
+                auto &o = ctx->pk_owned[f];
+                if (o.bytes != D * 32) o.alloc(D * 32);
+                up.push_back({o.p, src[f], D * 32});
+                dst[f] = o.u64();
+            }
+        }
+        h2d_batch(ctx, up);
+        // an all-zero optional selector is the zero polynomial too
+        for (int k = 0; k < 6; k++) {
+            const int f = kSelField[k];
+            if (dst[f] && !pnp::k_any_nonzero(dst[f], 4 * D, ctx->scratch_b, ctx->stream)) {
+                dst[f] = nullptr;
+                ctx->pk_owned[f].release();
+            }
+        }
+        ctx->pk_qm_zero = dev.q_m_coeffs == nullptr;
+        ctx->pk_qlookup_zero = dev.q_lookup_coeffs == nullptr;
+        ctx->pk_custom_nz[0] = dev.range_selector_coeffs != nullptr;
+        ctx->pk_custom_nz[1] = dev.logic_selector_coeffs != nullptr;
+        ctx->pk_custom_nz[2] = dev.fixed_group_add_selector_coeffs != nullptr;
+        ctx->pk_custom_nz[3] = dev.variable_group_add_selector_coeffs != nullptr;
+        uint32_t lg = 0;
+        while ((1ULL << lg) < D) lg++;
+        pk_sigma_domain(ctx, dev, D, lg);
+        ctx->pk_std_coset = true;  // a derived key has the standard coset by construction
+        pk_block_range(ctx);
+        const bool q29 = pk_q29_class(ctx, dev, D);
+        // every block array from its n coefficients, on the context's stream
+        // (the tables first: lde_blocks would build them lazily one by one)
+        pnp::ntt_warm(ctx->ntt, lg, ctx->stream);
+        std::vector<std::string> used, used29;
+        const uint64_t blk_elems = (uint64_t)ctx->pk_nb * D;
+        auto slot = [&](const char *name, bool form29) -> uint64_t * {
+            auto &b = (form29 ? ctx->pk_blk29 : ctx->pk_blk)[name];
+            if (b.bytes != 32 * blk_elems) b.alloc(32 * blk_elems);
+            (form29 ? used29 : used).push_back(name);
+            return b.u64();
+        };
+        auto blk = [&](const char *name, const uint64_t *coeffs) {
+            const bool form29 = q29 && pk_name_in29(name);
+            pnp::lde_blocks(ctx->ntt, coeffs, slot(name, form29), lg, ctx->pk_mb0, ctx->pk_nb, ctx->stream, form29);
+        };
+        if (!ctx->pk_qm_zero) blk("q_m", dev.q_m_coeffs);
+        if (!ctx->pk_qlookup_zero) blk("q_lookup", dev.q_lookup_coeffs);
+        if (ctx->pk_custom_nz[0]) blk("range", dev.range_selector_coeffs);
+        if (ctx->pk_custom_nz[1]) blk("logic", dev.logic_selector_coeffs);
+        if (ctx->pk_custom_nz[2]) blk("fixed_add", dev.fixed_group_add_selector_coeffs);
+        if (ctx->pk_custom_nz[3]) blk("var_add", dev.variable_group_add_selector_coeffs);
+        blk("q_l", dev.q_l_coeffs);
+        blk("q_r", dev.q_r_coeffs);
+        blk("q_o", dev.q_o_coeffs);
+        blk("q_4", dev.q_4_coeffs);
+        blk("q_c", dev.q_c_coeffs);
+        blk("q_hl", dev.q_hl_coeffs);
+        blk("q_hr", dev.q_hr_coeffs);
+        blk("q_h4", dev.q_h4_coeffs);
+        blk("q_arith", dev.q_arith_coeffs);
+        blk("sig0", dev.left_sigma_coeffs);
+        blk("sig1", dev.right_sigma_coeffs);
+        blk("sig2", dev.out_sigma_coeffs);
+        blk("sig3", dev.fourth_sigma_coeffs);
+        // the coset constants from their closed forms, straight into the
+        // blocks: lin (2^256 form always: the PI term), its 2^261 form for a
+        // q29 key, v_h^-1, and D (lin - 1), inverted in place into l1v
+        {
+            uint64_t *lin = slot("lin", false), *lin29 = q29 ? slot("lin", true) : nullptr;
+            uint64_t *vh_inv = slot("vh_inv", false), *l1v = slot("l1v", false);
+            pnp::k_coset_blocks(lg, ctx->pk_mb0, ctx->pk_nb, lin, lin29, vh_inv, l1v, ctx->stream);
+            pnp::k_batch_inverse(l1v, blk_elems, ctx->scratch_a, ctx->stream);
+        }
+        pk_prune_blocks(ctx->pk_blk, used);
+        pk_prune_blocks(ctx->pk_blk29, used29);
+        ctx->pk_q29 = q29;
+        // the natural-order scratch of an earlier full load is not needed again
         PNP_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->pk_dev = dev;
-        ctx->pk_n = D;
-        ctx->pk_loaded = true;
-        ctx->hbm_checked = false;  // the budget is checked by the next proof (pnp::hbm_budget)
+        for (auto &b : ctx->pk_tmp) b.release();
+        pk_load_done(ctx, dev, D);
     });
 }
 
@@ -1531,6 +1676,148 @@ uint64_t ck_fingerprint(const CommitKeyC &ck, uint64_t D) {
     return ck.powers_of_g ? sample_words(h, ck.powers_of_g, 12 * D) : h;
 }
 
+// PNP_V1_DERIVE=1 (opt-in, for callers whose prover key is what the
+// reference's preprocessing produces: every *_evals array the coset FFT of its
+// *_coeffs, linear_evaluations and v_h_coset_8n the standard coset's): wherever
+// gen_proof decides the prover key must be (re)loaded it is loaded through
+// pnp_load_prover_key_coeffs, so the 8n arrays (~17 GiB at HEIGHT=15) are not
+// uploaded.  WHETHER the key changed is decided as without the switch (content
+// hash, REUSE fingerprint, RELOAD).  A v1 caller cannot say which optional
+// selectors exist (their coefficient Vecs are empty, dangling pointers), so
+// that is read from the evaluations: a selector is the zero polynomial iff its
+// first D evaluations are zero — exact for a consistent key, a non-zero
+// polynomial of degree < D has fewer than D roots.  After the derivation the
+// Fr elements holding the 257 sampled words (sample_words) of every 8n array
+// the full load would have read are compared with the derived blocks; on a
+// mismatch the full key is uploaded instead (same proof as the default, no
+// error).  An inconsistency in unsampled elements is not seen: that is the
+// caller's promise, like PNP_V1_REUSE's.
+struct V1KeyLoad {
+    bool derive = false;                              // the switch, this call
+    bool tried = false, derived = false, fell_back = false;
+    double ms_scan = 0, ms_derive = 0, ms_fallback = 0;
+};
+// block name of the 8n array in ProverKeyC field f (nullptr: not an 8n array)
+const char *pk_eval_block(int f) {
+    static const char *const names[44] = {
+        nullptr, "q_m", nullptr, "q_l", nullptr, "q_r", nullptr, "q_o", nullptr, "q_4", nullptr, "q_c",
+        nullptr, "q_hl", nullptr, "q_hr", nullptr, "q_h4", nullptr, "q_arith", nullptr, "range",
+        nullptr, "logic", nullptr, "fixed_add", nullptr, "var_add", nullptr, "q_lookup",
+        nullptr, nullptr, nullptr, nullptr, nullptr, "sig0", nullptr, "sig1", nullptr, "sig2",
+        nullptr, "sig3", "lin", "vh_inv"};
+    return names[f];
+}
+// the sampled elements of the caller's 8n arrays against the derived blocks
+// (gathered on the device from the block layout; the blocks another rank owns
+// are skipped); false: some element differs
+bool v1_sampled_check(pnp_ctx *ctx, const ProverKeyC &pk, uint64_t D) {
+    uint64_t *const *f = reinterpret_cast<uint64_t *const *>(&pk);
+    const uint64_t K = 256, words = 4 * 8 * D;
+    uint32_t lg = 0;
+    while ((1ULL << lg) < D) lg++;
+    std::vector<uint64_t> idx(K + 1);
+    for (uint64_t k = 0; k <= K; k++) idx[k] = ((words - 1) * k / K) / 4;  // element of sampled word k
+    const uint32_t cnt = (uint32_t)idx.size();
+    struct Arr {
+        int field;
+        int form;  // 0: zero selector, 1: 2^256 form, 2: 2^261 form (x 32), 3: the inverse (v_h)
+    };
+    std::vector<Arr> arrs;
+    std::vector<const uint64_t *> blks;
+    for (int i = 0; i < 44; i++) {
+        const char *name = pk_eval_block(i);
+        if (!name) continue;
+        if (!f[i]) return false;  // the full load refuses it: let it say so
+        const uint64_t *b = ctx->blk(name), *b29 = ctx->blk29(name);
+        arrs.push_back({i, i == 43 ? 3 : b ? 1 : b29 ? 2 : 0});
+        blks.push_back(b ? b : b29);
+    }
+    pnp::DevBuf d_idx(8 * cnt), d_out(32 * (size_t)cnt * arrs.size());
+    std::vector<uint64_t> got(4 * (size_t)cnt * arrs.size());
+    PNP_HIP(hipMemcpyAsync(d_idx.p, idx.data(), 8 * cnt, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t a = 0; a < arrs.size(); a++)
+        if (blks[a])
+            pnp::k_gather_blocks(blks[a], lg, ctx->pk_mb0, ctx->pk_nb, d_idx.u64(), cnt, d_out.u64() + 4 * cnt * a,
+                                 ctx->stream);
+    PNP_HIP(hipMemcpyAsync(got.data(), d_out.p, 8 * got.size(), hipMemcpyDeviceToHost, ctx->stream));
+    PNP_HIP(hipStreamSynchronize(ctx->stream));
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    uint64_t one[4];
+    to_u64_limbs(Fr::one(), one);
+    for (size_t a = 0; a < arrs.size(); a++) {
+        const uint64_t *src = f[arrs[a].field];
+        for (uint32_t k = 0; k < cnt; k++) {
+            const int m = (int)(idx[k] & 7);
+            const uint64_t *mine = src + 4 * idx[k], *dev = &got[4 * (cnt * a + k)];
+            if (arrs[a].form == 0) {  // the zero polynomial: zero everywhere, whoever owns the block
+                if (memcmp(mine, zero, 32)) return false;
+                continue;
+            }
+            if (m < ctx->pk_mb0 || m >= ctx->pk_mb0 + ctx->pk_nb) continue;
+            uint64_t want[4];
+            if (arrs[a].form == 1) {
+                memcpy(want, mine, 32);
+            } else if (arrs[a].form == 2) {
+                Fr x = from_u64_limbs<FrP>(mine);
+                for (int d = 0; d < 5; d++) x = x + x;
+                to_u64_limbs(x, want);
+            } else {  // v_h times the derived v_h^-1 is one
+                to_u64_limbs(from_u64_limbs<FrP>(mine) * from_u64_limbs<FrP>(dev), want);
+                dev = one;
+            }
+            if (memcmp(want, dev, 32)) return false;
+        }
+    }
+    return true;
+}
+// the prover-key load of gen_proof: the full upload, or with PNP_V1_DERIVE
+// the coefficient path with its zero scan, sampled check and fallback
+int v1_load_prover_key(pnp_ctx *ctx, const ProverKeyC &pk, uint64_t D, V1KeyLoad &st, unsigned cap = 0) {
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+    if (!st.derive) return pnp_load_prover_key(ctx, &pk, D, 0);
+    st.tried = true;
+    uint64_t *const *f = reinterpret_cast<uint64_t *const *>(&pk);
+    bool usable = true;
+    for (int k = 0; k < 6; k++) usable &= f[kSelField[k] + 1] != nullptr;
+    if (usable) {
+        // which optional selectors exist: their first D evaluations, scanned on
+        // the hash thread pool
+        auto t = clk::now();
+        std::vector<Seg> segs;
+        for (int k = 0; k < 6; k++) segs.push_back({f[kSelField[k] + 1], 4 * D});
+        const std::vector<SegHash> h = hash_segments(segs, cap);
+        ProverKeyC compact = pk;
+        uint64_t **c = reinterpret_cast<uint64_t **>(&compact);
+        for (int k = 0; k < 6; k++)
+            if (!h[k].nz) c[kSelField[k]] = nullptr;
+        st.ms_scan = ms_since(t);
+        t = clk::now();
+        bool ok = pnp_load_prover_key_coeffs(ctx, &compact, D, 0) == PNP_OK;
+        try {
+            ok = ok && v1_sampled_check(ctx, pk, D);
+        } catch (const Error &) {
+            ok = false;
+        }
+        st.ms_derive = ms_since(t);
+        if (ok) {
+            st.derived = true;
+            return PNP_OK;
+        }
+    }
+    const auto t = clk::now();
+    st.fell_back = true;
+    const int rc = pnp_load_prover_key(ctx, &pk, D, 0);
+    st.ms_fallback = ms_since(t);
+    return rc;
+}
+void v1_key_stages(const V1KeyLoad &st, std::vector<std::pair<std::string, double>> &out) {
+    if (!st.tried) return;
+    out.push_back({"v1_zero_scan", st.ms_scan});
+    out.push_back({"v1_derive_key", st.ms_derive});
+    if (st.fell_back) out.push_back({"v1_derive_fallback", st.ms_fallback});
+}
+
 }  // namespace
 
 // The folded MSM table of a freshly uploaded SRS (what a context's first proof
@@ -1574,6 +1861,13 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
         return e && atoi(e) != 0;
     };
     const bool reuse = env_on("PNP_V1_REUSE"), reload = env_on("PNP_V1_RELOAD"), strict = env_on("PNP_V1_STRICT");
+    // PNP_V1_DERIVE (see V1KeyLoad): a resident key that was derived stands
+    // for the caller's arrays only under the switch's promise; a call without
+    // the switch uploads the caller's own arrays again
+    static bool pk_derived = false;
+    V1KeyLoad kl;
+    kl.derive = env_on("PNP_V1_DERIVE");
+    if (pk_derived && !kl.derive) have_pk = false;
     ProofC out;
     memset(&out, 0, sizeof out);
     auto die = [](int rc) {
@@ -1590,6 +1884,7 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
     const bool cold_ctx = !ctx;
     if (!ctx && (rc = pnp_ctx_create(0, &ctx)) != PNP_OK) die(rc);
     const double ms_ctx = cold_ctx ? ms_since(t_call) : 0.0;
+    double ms_pk_warm = 0;
     uint64_t bound = circuit.n > circuit.lookup_len ? circuit.n : circuit.lookup_len;
     uint64_t D = 1;
     while (D < bound) D <<= 1;
@@ -1666,9 +1961,10 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
                     ms_ck = ms_since(t);
                     if (ctx->msm.world <= 1 && ctx->ck_table_n != D) tb = table_prebuild(ctx, D);
                     t = clk::now();
-                    lrc = pnp_load_prover_key(ctx, &pk, D, 0);
+                    lrc = v1_load_prover_key(ctx, pk, D, kl, cap);
                     if (tb.joinable()) tb.join();
                     if (lrc == PNP_OK) {
+                        pk_derived = kl.derived;
                         envelope = !strict || (ctx->pk_qm_zero && ctx->pk_qlookup_zero && !ctx->pk_custom_nz[0] &&
                                                !ctx->pk_custom_nz[1] && !ctx->pk_custom_nz[2] &&
                                                !ctx->pk_custom_nz[3] && key_tables_zero(ctx));
@@ -1689,6 +1985,7 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
                 std::vector<std::pair<std::string, double>> st = {
                     {"v1_ctx_create", ms_ctx}, {"v1_load_prover_key", ms_pk}, {"v1_load_commit_key", ms_ck},
                     {"v1_prove", ms_prove}};
+                v1_key_stages(kl, st);
                 st.insert(st.end(), ctx->stages.begin(), ctx->stages.end());
                 st.push_back({"v1_hash_wait", ms_since(t_join)});
                 st.push_back({"v1_call", ms_since(t_call)});
@@ -1713,7 +2010,10 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
     }
     if (reload || !have_pk || hp != h_pk || !ctx->pk_loaded || ctx->pk_n != D) {
         have_pk = false;
-        if ((rc = pnp_load_prover_key(ctx, &pk, D, 0)) != PNP_OK) die(rc);
+        const auto t_pk = clk::now();
+        if ((rc = v1_load_prover_key(ctx, pk, D, kl)) != PNP_OK) die(rc);
+        ms_pk_warm = ms_since(t_pk);
+        pk_derived = kl.derived;
         if (strict && (!ctx->pk_qm_zero || !ctx->pk_qlookup_zero || ctx->pk_custom_nz[0] ||
                        ctx->pk_custom_nz[1] || ctx->pk_custom_nz[2] || ctx->pk_custom_nz[3] ||
                        !key_tables_zero(ctx))) {
@@ -1731,6 +2031,12 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
         h_ck = hc;
     }
     if ((rc = pnp_prove(ctx, &circuit, 0, &out)) != PNP_OK) die(rc);
+    if (kl.tried) {  // PNP_V1_DERIVE: the key load's stages before the proof's
+        std::vector<std::pair<std::string, double>> st = {{"v1_load_prover_key", ms_pk_warm}};
+        v1_key_stages(kl, st);
+        st.insert(st.end(), ctx->stages.begin(), ctx->stages.end());
+        ctx->stages.swap(st);
+    }
     return out;
 }
 

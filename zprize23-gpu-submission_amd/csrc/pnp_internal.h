@@ -285,6 +285,16 @@ void k_random_fr(uint64_t *d, uint64_t n, uint64_t seed, hipStream_t s);
 void k_geometric(uint64_t *d, uint64_t n, const Fr &c0, const Fr &r, hipStream_t s);
 void k_srs(uint64_t *d, uint64_t n, const Fr &tau, hipStream_t s);
 void k_coset_consts(uint64_t *vh, uint64_t *x, uint32_t lg_n, hipStream_t s);
+// ---- key-load kernels (keyblocks.hip) ----
+// the coset constants of blocks m0 .. m0 + nb - 1 in block-bitrev layout from
+// their closed forms (coset_blocks.cuh): lin, lin32 = 32 lin (the 2^261 form),
+// vh_inv, and l1_den = D (lin - 1), whose inverse is l1v; nullptr = not wanted
+void k_coset_blocks(uint32_t lg_n, int m0, int nb, uint64_t *lin, uint64_t *lin32, uint64_t *vh_inv,
+                    uint64_t *l1_den, hipStream_t s);
+// d_out[k] = the point with natural index d_idx[k] (< 8n) of a block-layout
+// array holding blocks m0 .. m0 + nb - 1 (zero when its block is not held)
+void k_gather_blocks(const uint64_t *blk, uint32_t lg_n, int m0, int nb, const uint64_t *d_idx, uint32_t cnt,
+                     uint64_t *d_out, hipStream_t s);
 void k_synth_merkle(int height, const uint64_t *pc_mont_host, const uint64_t *leaves, const uint64_t *blind,
                     uint64_t *nodes, uint64_t *const w[4], uint64_t *const sel[9], uint64_t *const sigma[4],
                     uint64_t n, hipStream_t s);

@@ -27,7 +27,7 @@ ERRORS = {-1: "PNP_E_ARG", -2: "PNP_E_DEVICE", -3: "PNP_E_NOKEY", -4: "PNP_E_ENV
 
 # exported symbols declared by include/pnp_plonk.h (checked by tests/test_abi.py)
 SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
-           "pnp_load_prover_key", "pnp_load_commit_key", "pnp_prove", "pnp_prove_ex",
+           "pnp_load_prover_key", "pnp_load_prover_key_coeffs", "pnp_load_commit_key", "pnp_prove", "pnp_prove_ex",
            "pnp_last_stage_times",
            "pnp_kernel_timing", "pnp_kernel_stats", "pnp_kernel_bytes", "pnp_set_msm_shard",
            "pnp_set_exchange_a2a",
@@ -76,6 +76,7 @@ def load(path: str = LIB_PATH):
     lib.pnp_ctx_destroy.argtypes = [vp]
     lib.pnp_ctx_destroy.restype = None
     lib.pnp_load_prover_key.argtypes = [vp, C.POINTER(abi.ProverKeyC), u64, i32]
+    lib.pnp_load_prover_key_coeffs.argtypes = [vp, C.POINTER(abi.ProverKeyC), u64, i32]
     lib.pnp_load_commit_key.argtypes = [vp, C.POINTER(abi.CommitKeyC), u64, i32]
     lib.pnp_prove.argtypes = [vp, C.POINTER(abi.CircuitC), i32, C.POINTER(abi.ProofC)]
     lib.pnp_prove_ex.argtypes = [vp, C.POINTER(abi.CircuitC), i32, u64, vp, vp, C.c_char_p,
@@ -160,6 +161,13 @@ class Context:
     def load_prover_key(self, pk: abi.ProverKeyC, domain: int, device_ptrs: bool):
         check(self.lib.pnp_load_prover_key(self.h, C.byref(pk), domain, int(device_ptrs)),
               "pnp_load_prover_key")
+
+    def load_prover_key_coeffs(self, pk: abi.ProverKeyC, domain: int, device_ptrs: bool):
+        """pnp_load_prover_key_coeffs: the resident key from the coefficient
+        arrays and tables alone (the 8n arrays are derived on the GPU; the
+        *_evals fields may be NULL, an absent optional selector is NULL)."""
+        check(self.lib.pnp_load_prover_key_coeffs(self.h, C.byref(pk), domain, int(device_ptrs)),
+              "pnp_load_prover_key_coeffs")
 
     def load_commit_key(self, ck: abi.CommitKeyC, n_points: int, device_ptrs: bool):
         check(self.lib.pnp_load_commit_key(self.h, C.byref(ck), n_points, int(device_ptrs)),
