@@ -284,6 +284,60 @@ int pnp_load_commit_key(pnp_ctx *ctx, const CommitKeyC *ck, uint64_t n_points,
 int pnp_load_prover_key_coeffs(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t domain_size,
                                int device_ptrs);
 
+/* Preprocessing on the GPU: the resident prover key, and the verifier key,
+ * from what a composer holds — selector columns, the wire map, lookup tables —
+ * instead of StandardComposer::preprocess_shared on the CPU (preprocess.rs:
+ * 318-520: 15 selector iFFTs, the copy permutation over a
+ * HashMap<Variable, Vec<WireData>> (permutation/mod.rs:101-213), 4 sigma and 4
+ * table iFFTs, 23 commitments).
+ *   D = next_pow2(max(n_gates, lookup_len)), 1 <= n_gates, D <= 2^25.
+ *   var[j][i] : the variable in wire j (0 left, 1 right, 2 out, 3 fourth) of
+ *     gate i (Variable is a usize in Rust: narrow to u32), each < n_vars.  The
+ *     composer registers a gate's wires in the order L, R, O, 4 and gates in
+ *     row order, so the slots of a variable are ordered by (row, wire) and each
+ *     maps to the next, the last to the first (compute_sigma_permutations);
+ *     rows >= n_gates map to themselves.
+ *   sel[k][i] : the selector ROW VALUES (not coefficients), zero-padded to D
+ *     here; NULL = a zero column.  An all-zero q_m, custom-gate or q_lookup
+ *     column is the zero polynomial whether NULL or not.
+ *   table[k]  : lookup_len entries each, padded to D with the first entry
+ *     (MultiSet::pad); all zero when lookup_len == 0 (table[] ignored).
+ * The columns are padded, inverse-transformed into arrays the context owns,
+ * the sigmas built from the wire map on the device, and the 8n arrays derived
+ * exactly as by pnp_load_prover_key_coeffs: afterwards the context is in the
+ * state that call leaves for the reference's preprocessed key of this circuit
+ * (proofs are the same bytes).  With `vk` non-NULL the 23 commitments are
+ * computed against the resident commit key (pnp_load_commit_key first).
+ * device_ptrs: var / sel / table are HBM pointers (read, not adopted).
+ * Synchronous; the sort scratch is released before it returns.
+ * Errors, all decided before the resident key is touched (it keeps proving):
+ *   PNP_E_ARG    n_gates = 0, D > 2^25, a NULL var[j], a NULL table[j] with
+ *                lookup_len > 0, a variable id >= n_vars (wire and row in
+ *                pnp_last_error), or a context sharded over several ranks
+ *                (pnp_set_msm_shard world > 1: multi-rank preprocessing is not
+ *                supported; preprocess on one rank and load the coefficients)
+ *   PNP_E_NOKEY  vk wanted without a commit key of >= D points */
+#define PNP_VK_POLYS 23
+/* layout-identical to the oracle's or_verifier_key: n, g = SRS_0, then q_m q_l q_r q_o q_4 q_c
+ * q_hl q_hr q_h4 q_arith range logic fixed_group_add variable_group_add left/right/out/fourth
+ * sigma q_lookup table_1..4; the zero polynomial is the header's infinity (x = 0, y = Fq one) */
+typedef struct { uint64_t n; uint64_t g[12]; CommitmentC polys[PNP_VK_POLYS]; } pnp_verifier_key;
+
+typedef struct {
+    uint64_t n_gates, n_vars, lookup_len;
+    const uint32_t *var[4];    /* n_gates each */
+    const uint64_t *sel[15];   /* q_m q_l q_r q_o q_4 q_c q_hl q_hr q_h4 q_arith range logic
+                                  fixed_group_add variable_group_add q_lookup: n_gates Montgomery Fr
+                                  each (row evaluations, NOT coefficients); NULL = zero column */
+    const uint64_t *table[4];  /* lookup_len Montgomery Fr each; ignored when lookup_len == 0 */
+} pnp_circuit_desc;
+
+/* Until the next proof, pnp_last_stage_times reports this call's stages
+ * (pre_upload, pre_permutation, pre_intt, pre_derive, pre_vk; milliseconds) and
+ * two counts in the same list: pre_permutation_bytes, what the permutation
+ * kernels had to move, and pre_h2d_bytes, what crossed PCIe. */
+int pnp_preprocess(pnp_ctx *ctx, const pnp_circuit_desc *c, int device_ptrs, pnp_verifier_key *vk /* may be NULL */);
+
 /* The commit key straight from arkworks' memory, without the per-proof
  * conversion prove_pnp does today (prover.rs:700-711 rebuilds (x, y) tuples
  * of all 2^24+1 SRS points on every call): `points` = the address of
@@ -474,6 +528,19 @@ int pnp_commit_segments(pnp_ctx *ctx, const uint64_t *d_points, uint64_t n_point
                         const uint64_t *seg_off, const uint64_t *const *d_scalars, uint64_t n,
                         CommitmentC *out);
 
+/* Extension (operator form of pnp_preprocess' permutation kernels,
+ * preprocess.hip): the copy permutation of a wire map on the domain
+ * D = 2^lg_n >= n_gates (lg_n <= 25).  d_var[j]: n_gates variable ids of wire
+ * j in HBM, each < n_vars.  d_next (4 D u32): d_next[j D + i] = j' D + i', the
+ * slot after (wire j, row i) among the slots of its variable in (row, wire)
+ * order, cyclically; rows >= n_gates map to themselves.  d_sigma[j] (D
+ * Montgomery Fr each): sigma_j(w^i) = K_j' w^i', K = (1, 7, 13, 17).  Either
+ * output may be NULL (d_sigma, or single columns of it).  Synchronous.
+ * PNP_E_ARG with the wire and row in pnp_last_error when an id is >= n_vars
+ * (the outputs are then unspecified). */
+int pnp_wire_sigma(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars,
+                   uint32_t lg_n, uint32_t *d_next, uint64_t *const d_sigma[4]);
+
 /* evaluate (function.cu:162-173): sum_i c_i x^i; x and result Montgomery,
  * host-side scalars.  Synchronous. */
 int pnp_poly_eval(pnp_ctx *ctx, const uint64_t *d_coeffs, uint64_t n,
@@ -534,6 +601,8 @@ static_assert(sizeof(ProofC) == 2656, "ProofC layout (lib.rs:120-142)");
 static_assert(sizeof(CircuitC) == 72, "CircuitC layout (lib.rs:144-155)");
 static_assert(sizeof(ProverKeyC) == 44 * 8, "ProverKeyC layout (lib.rs:157-223)");
 static_assert(sizeof(CommitKeyC) == 16, "CommitKeyC layout (lib.rs:225-229)");
+static_assert(sizeof(pnp_verifier_key) == 8 + 96 + PNP_VK_POLYS * 96, "pnp_verifier_key layout (or_verifier_key)");
+static_assert(sizeof(pnp_circuit_desc) == 3 * 8 + (4 + 15 + 4) * 8, "pnp_circuit_desc layout");
 #else
 _Static_assert(sizeof(ProofC) == 2656, "ProofC layout (lib.rs:120-142)");
 _Static_assert(sizeof(ProverKeyC) == 44 * 8, "ProverKeyC layout (lib.rs:157-223)");

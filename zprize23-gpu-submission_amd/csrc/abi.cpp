@@ -1079,6 +1079,84 @@ void pk_load_done(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D) {
     ctx->hbm_checked = false;  // the budget is checked by the next proof (pnp::hbm_budget)
 }
 
+// The resident key from its coefficient arrays in HBM (`dev`: the *_coeffs and
+// table fields set, NULL = absent), shared by pnp_load_prover_key_coeffs and
+// pnp_preprocess: drops all-zero optional selectors, derives every block
+// array by the per-proof LDE and the coset constants from closed forms.
+void pk_derive_from_coeffs(pnp_ctx *ctx, ProverKeyC &dev, uint64_t D) {
+    uint64_t **dst = reinterpret_cast<uint64_t **>(&dev);
+    // an all-zero optional selector is the zero polynomial too
+    for (int k = 0; k < 6; k++) {
+        const int f = kSelField[k];
+        if (dst[f] && !pnp::k_any_nonzero(dst[f], 4 * D, ctx->scratch_b, ctx->stream)) {
+            dst[f] = nullptr;
+            ctx->pk_owned[f].release();
+        }
+    }
+    ctx->pk_qm_zero = dev.q_m_coeffs == nullptr;
+    ctx->pk_qlookup_zero = dev.q_lookup_coeffs == nullptr;
+    ctx->pk_custom_nz[0] = dev.range_selector_coeffs != nullptr;
+    ctx->pk_custom_nz[1] = dev.logic_selector_coeffs != nullptr;
+    ctx->pk_custom_nz[2] = dev.fixed_group_add_selector_coeffs != nullptr;
+    ctx->pk_custom_nz[3] = dev.variable_group_add_selector_coeffs != nullptr;
+    uint32_t lg = 0;
+    while ((1ULL << lg) < D) lg++;
+    pk_sigma_domain(ctx, dev, D, lg);
+    ctx->pk_std_coset = true;  // a derived key has the standard coset by construction
+    pk_block_range(ctx);
+    const bool q29 = pk_q29_class(ctx, dev, D);
+    // every block array from its n coefficients, on the context's stream
+    // (the tables first: lde_blocks would build them lazily one by one)
+    pnp::ntt_warm(ctx->ntt, lg, ctx->stream);
+    std::vector<std::string> used, used29;
+    const uint64_t blk_elems = (uint64_t)ctx->pk_nb * D;
+    auto slot = [&](const char *name, bool form29) -> uint64_t * {
+        auto &b = (form29 ? ctx->pk_blk29 : ctx->pk_blk)[name];
+        if (b.bytes != 32 * blk_elems) b.alloc(32 * blk_elems);
+        (form29 ? used29 : used).push_back(name);
+        return b.u64();
+    };
+    auto blk = [&](const char *name, const uint64_t *coeffs) {
+        const bool form29 = q29 && pk_name_in29(name);
+        pnp::lde_blocks(ctx->ntt, coeffs, slot(name, form29), lg, ctx->pk_mb0, ctx->pk_nb, ctx->stream, form29);
+    };
+    if (!ctx->pk_qm_zero) blk("q_m", dev.q_m_coeffs);
+    if (!ctx->pk_qlookup_zero) blk("q_lookup", dev.q_lookup_coeffs);
+    if (ctx->pk_custom_nz[0]) blk("range", dev.range_selector_coeffs);
+    if (ctx->pk_custom_nz[1]) blk("logic", dev.logic_selector_coeffs);
+    if (ctx->pk_custom_nz[2]) blk("fixed_add", dev.fixed_group_add_selector_coeffs);
+    if (ctx->pk_custom_nz[3]) blk("var_add", dev.variable_group_add_selector_coeffs);
+    blk("q_l", dev.q_l_coeffs);
+    blk("q_r", dev.q_r_coeffs);
+    blk("q_o", dev.q_o_coeffs);
+    blk("q_4", dev.q_4_coeffs);
+    blk("q_c", dev.q_c_coeffs);
+    blk("q_hl", dev.q_hl_coeffs);
+    blk("q_hr", dev.q_hr_coeffs);
+    blk("q_h4", dev.q_h4_coeffs);
+    blk("q_arith", dev.q_arith_coeffs);
+    blk("sig0", dev.left_sigma_coeffs);
+    blk("sig1", dev.right_sigma_coeffs);
+    blk("sig2", dev.out_sigma_coeffs);
+    blk("sig3", dev.fourth_sigma_coeffs);
+    // the coset constants from their closed forms, straight into the
+    // blocks: lin (2^256 form always: the PI term), its 2^261 form for a
+    // q29 key, v_h^-1, and D (lin - 1), inverted in place into l1v
+    {
+        uint64_t *lin = slot("lin", false), *lin29 = q29 ? slot("lin", true) : nullptr;
+        uint64_t *vh_inv = slot("vh_inv", false), *l1v = slot("l1v", false);
+        pnp::k_coset_blocks(lg, ctx->pk_mb0, ctx->pk_nb, lin, lin29, vh_inv, l1v, ctx->stream);
+        pnp::k_batch_inverse(l1v, blk_elems, ctx->scratch_a, ctx->stream);
+    }
+    pk_prune_blocks(ctx->pk_blk, used);
+    pk_prune_blocks(ctx->pk_blk29, used29);
+    ctx->pk_q29 = q29;
+    // the natural-order scratch of an earlier full load is not needed again
+    PNP_HIP(hipStreamSynchronize(ctx->stream));
+    for (auto &b : ctx->pk_tmp) b.release();
+    pk_load_done(ctx, dev, D);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1283,76 +1361,220 @@ int pnp_load_prover_key_coeffs(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, i
             }
         }
         h2d_batch(ctx, up);
-        // an all-zero optional selector is the zero polynomial too
-        for (int k = 0; k < 6; k++) {
-            const int f = kSelField[k];
-            if (dst[f] && !pnp::k_any_nonzero(dst[f], 4 * D, ctx->scratch_b, ctx->stream)) {
-                dst[f] = nullptr;
-                ctx->pk_owned[f].release();
-            }
+        pk_derive_from_coeffs(ctx, dev, D);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+// pnp_circuit_desc.sel[k] -> its coefficient field of ProverKeyC, and whether
+// an absent column leaves the field NULL (kSelField) or is a column of zeros
+const int kDescSelField[15] = {0, 2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28};
+const bool kDescSelOptional[15] = {true, false, false, false, false, false, false, false,
+                                   false, false, true, true, true, true, true};
+const int kTableField[4] = {30, 31, 32, 33};
+const int kSigmaField[4] = {34, 36, 38, 40};
+// pnp_verifier_key.polys[k] -> the ProverKeyC field holding its polynomial
+// (the tables are kept as padded columns: committed from a transformed copy)
+const int kVkField[PNP_VK_POLYS] = {0,  2,  4,  6,  8,  10, 12, 14, 16, 18, 20, 22,
+                                    24, 26, 34, 36, 38, 40, 28, 30, 31, 32, 33};
+
+bool bad_variable(uint64_t slot, uint64_t n_vars) {
+    if (slot == ~0ULL) return false;
+    set_error("variable id >= n_vars (%llu) in wire %d of row %llu", (unsigned long long)n_vars, (int)(slot & 3),
+              (unsigned long long)(slot >> 2));
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnp_wire_sigma(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, uint32_t lg_n,
+                   uint32_t *d_next, uint64_t *const d_sigma[4]) {
+    if (!ctx || !d_var || !d_var[0] || !d_var[1] || !d_var[2] || !d_var[3] || n_gates == 0 || lg_n > 25 ||
+        n_gates > (1ULL << lg_n))
+        return PNP_E_ARG;
+    PNP_TRY({
+        tables_wait(ctx);  // (the NTT tables are shared with a background build)
+        PNP_HIP(hipSetDevice(ctx->device));
+        pnp::DevBuf next, sort;
+        if (!d_next) {
+            next.alloc(16ULL << lg_n);
+            d_next = static_cast<uint32_t *>(next.p);
         }
-        ctx->pk_qm_zero = dev.q_m_coeffs == nullptr;
-        ctx->pk_qlookup_zero = dev.q_lookup_coeffs == nullptr;
-        ctx->pk_custom_nz[0] = dev.range_selector_coeffs != nullptr;
-        ctx->pk_custom_nz[1] = dev.logic_selector_coeffs != nullptr;
-        ctx->pk_custom_nz[2] = dev.fixed_group_add_selector_coeffs != nullptr;
-        ctx->pk_custom_nz[3] = dev.variable_group_add_selector_coeffs != nullptr;
-        uint32_t lg = 0;
-        while ((1ULL << lg) < D) lg++;
-        pk_sigma_domain(ctx, dev, D, lg);
-        ctx->pk_std_coset = true;  // a derived key has the standard coset by construction
-        pk_block_range(ctx);
-        const bool q29 = pk_q29_class(ctx, dev, D);
-        // every block array from its n coefficients, on the context's stream
-        // (the tables first: lde_blocks would build them lazily one by one)
-        pnp::ntt_warm(ctx->ntt, lg, ctx->stream);
-        std::vector<std::string> used, used29;
-        const uint64_t blk_elems = (uint64_t)ctx->pk_nb * D;
-        auto slot = [&](const char *name, bool form29) -> uint64_t * {
-            auto &b = (form29 ? ctx->pk_blk29 : ctx->pk_blk)[name];
-            if (b.bytes != 32 * blk_elems) b.alloc(32 * blk_elems);
-            (form29 ? used29 : used).push_back(name);
-            return b.u64();
+        const uint64_t bad =
+            pnp::wire_sigma(ctx->ntt, d_var, n_gates, n_vars, lg_n, d_next, d_sigma, sort, ctx->stream);
+        if (bad_variable(bad, n_vars)) throw Error(PNP_E_ARG);
+    });
+}
+
+// Circuit::compile on the device: the padded columns and the sigmas of the
+// wire map inverse-transformed into the arrays pnp_load_prover_key_coeffs
+// would have been handed, then its derivation (pk_derive_from_coeffs), then
+// the verifier key's commitments.
+int pnp_preprocess(pnp_ctx *ctx, const pnp_circuit_desc *c, int device_ptrs, pnp_verifier_key *vk) {
+    if (!ctx || !c) return PNP_E_ARG;
+    const uint64_t ng = c->n_gates, tl = c->lookup_len;
+    if (ng == 0 || ng > (1ULL << 25) || tl > (1ULL << 25)) {
+        set_error("preprocess: %llu gates, %llu table rows (1 <= gates, domain <= 2^25)", (unsigned long long)ng,
+                  (unsigned long long)tl);
+        return PNP_E_ARG;
+    }
+    uint64_t D = 1;
+    uint32_t lg = 0;
+    while (D < std::max(ng, tl)) D <<= 1, lg++;
+    // every refusal comes before the resident key is touched
+    for (int j = 0; j < 4; j++) {
+        if (!c->var[j]) {
+            set_error("preprocess: var[%d] is null", j);
+            return PNP_E_ARG;
+        }
+        if (tl && !c->table[j]) {
+            set_error("preprocess: table[%d] is null with %llu table rows", j, (unsigned long long)tl);
+            return PNP_E_ARG;
+        }
+    }
+    if (ctx->msm.world > 1) {
+        set_error("preprocess: the context is sharded over %d ranks (multi-rank preprocessing is not supported)",
+                  ctx->msm.world);
+        return PNP_E_ARG;
+    }
+    if (vk && (!ctx->ck_loaded || ctx->ck_points < D)) {
+        set_error("preprocess: the verifier key needs a commit key of %llu points (%llu loaded)",
+                  (unsigned long long)D, (unsigned long long)(ctx->ck_loaded ? ctx->ck_points : 0));
+        return PNP_E_NOKEY;
+    }
+    PNP_TRY({
+        tables_wait(ctx);  // a background build reads the key being replaced: let it finish
+        PNP_HIP(hipSetDevice(ctx->device));
+        using clk = std::chrono::steady_clock;
+        double t_up = 0, t_perm = 0, t_intt = 0, t_derive = 0, t_vk = 0, h2d_bytes = 0;
+        auto t0 = clk::now();
+        auto lap = [&](double &acc) {  // (every stage ends synchronised)
+            PNP_HIP(hipStreamSynchronize(ctx->stream));
+            const auto t1 = clk::now();
+            acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
+            t0 = t1;
         };
-        auto blk = [&](const char *name, const uint64_t *coeffs) {
-            const bool form29 = q29 && pk_name_in29(name);
-            pnp::lde_blocks(ctx->ntt, coeffs, slot(name, form29), lg, ctx->pk_mb0, ctx->pk_nb, ctx->stream, form29);
-        };
-        if (!ctx->pk_qm_zero) blk("q_m", dev.q_m_coeffs);
-        if (!ctx->pk_qlookup_zero) blk("q_lookup", dev.q_lookup_coeffs);
-        if (ctx->pk_custom_nz[0]) blk("range", dev.range_selector_coeffs);
-        if (ctx->pk_custom_nz[1]) blk("logic", dev.logic_selector_coeffs);
-        if (ctx->pk_custom_nz[2]) blk("fixed_add", dev.fixed_group_add_selector_coeffs);
-        if (ctx->pk_custom_nz[3]) blk("var_add", dev.variable_group_add_selector_coeffs);
-        blk("q_l", dev.q_l_coeffs);
-        blk("q_r", dev.q_r_coeffs);
-        blk("q_o", dev.q_o_coeffs);
-        blk("q_4", dev.q_4_coeffs);
-        blk("q_c", dev.q_c_coeffs);
-        blk("q_hl", dev.q_hl_coeffs);
-        blk("q_hr", dev.q_hr_coeffs);
-        blk("q_h4", dev.q_h4_coeffs);
-        blk("q_arith", dev.q_arith_coeffs);
-        blk("sig0", dev.left_sigma_coeffs);
-        blk("sig1", dev.right_sigma_coeffs);
-        blk("sig2", dev.out_sigma_coeffs);
-        blk("sig3", dev.fourth_sigma_coeffs);
-        // the coset constants from their closed forms, straight into the
-        // blocks: lin (2^256 form always: the PI term), its 2^261 form for a
-        // q29 key, v_h^-1, and D (lin - 1), inverted in place into l1v
+        // the permutation first, into scratch: a bad id is an argument error
+        pnp::DevBuf sig[4];
         {
-            uint64_t *lin = slot("lin", false), *lin29 = q29 ? slot("lin", true) : nullptr;
-            uint64_t *vh_inv = slot("vh_inv", false), *l1v = slot("l1v", false);
-            pnp::k_coset_blocks(lg, ctx->pk_mb0, ctx->pk_nb, lin, lin29, vh_inv, l1v, ctx->stream);
-            pnp::k_batch_inverse(l1v, blk_elems, ctx->scratch_a, ctx->stream);
+            pnp::DevBuf vars, next(16 * D), sort;
+            const uint32_t *dvar[4] = {c->var[0], c->var[1], c->var[2], c->var[3]};
+            if (!device_ptrs) {
+                vars.alloc(16 * ng);
+                std::vector<H2D> up;
+                for (int j = 0; j < 4; j++) {
+                    uint32_t *d = static_cast<uint32_t *>(vars.p) + j * ng;
+                    up.push_back({d, c->var[j], 4 * ng});
+                    dvar[j] = d;
+                }
+                h2d_batch(ctx, up);
+                h2d_bytes += 16.0 * ng;
+            }
+            lap(t_up);
+            uint64_t *dsig[4];
+            for (int j = 0; j < 4; j++) {
+                sig[j].alloc(32 * D);
+                dsig[j] = sig[j].u64();
+            }
+            pnp::WireSigmaStats st;
+            const uint64_t bad = pnp::wire_sigma(ctx->ntt, dvar, ng, c->n_vars, lg, static_cast<uint32_t *>(next.p),
+                                                 dsig, sort, ctx->stream, &st);
+            if (bad_variable(bad, c->n_vars)) throw Error(PNP_E_ARG);
+            ctx->stages.clear();
+            ctx->stages.push_back({"pre_permutation_bytes", st.bytes});
+        }  // (the sort scratch, the id copies and next are released here)
+        lap(t_perm);
+        // ---- the resident key is replaced from here on
+        ctx->pk_loaded = false;
+        ctx->pk_gen++;
+        ctx->pk_owned.resize(44);
+        ProverKeyC dev{};
+        uint64_t **dst = reinterpret_cast<uint64_t **>(&dev);
+        for (int f = 0; f < 44; f++)
+            if (kPkKinds[f] != kCoeffs && kPkKinds[f] != kSelCoeffs && kPkKinds[f] != kTable)
+                ctx->pk_owned[f].release();
+        std::vector<H2D> up;
+        auto column = [&](int f, const uint64_t *src, uint64_t len, bool first) {
+            auto &o = ctx->pk_owned[f];
+            if (o.bytes != D * 32) o.alloc(D * 32);
+            dst[f] = o.u64();
+            if (!src || !len) {
+                PNP_HIP(hipMemsetAsync(o.p, 0, D * 32, ctx->stream));
+            } else if (device_ptrs) {
+                pnp::k_pad_col(o.u64(), src, len, D, first, ctx->stream);
+            } else {
+                up.push_back({o.p, src, len * 32});
+                h2d_bytes += 32.0 * len;
+            }
+        };
+        for (int k = 0; k < 15; k++) {
+            const int f = kDescSelField[k];
+            if (!c->sel[k] && kDescSelOptional[k]) ctx->pk_owned[f].release();
+            else column(f, c->sel[k], ng, false);
         }
-        pk_prune_blocks(ctx->pk_blk, used);
-        pk_prune_blocks(ctx->pk_blk29, used29);
-        ctx->pk_q29 = q29;
-        // the natural-order scratch of an earlier full load is not needed again
-        PNP_HIP(hipStreamSynchronize(ctx->stream));
-        for (auto &b : ctx->pk_tmp) b.release();
-        pk_load_done(ctx, dev, D);
+        for (int j = 0; j < 4; j++) column(kTableField[j], tl ? c->table[j] : nullptr, tl, true);
+        if (!device_ptrs) {
+            h2d_batch(ctx, up);
+            for (int k = 0; k < 15; k++)
+                if (c->sel[k]) pnp::k_pad_col(dst[kDescSelField[k]], dst[kDescSelField[k]], ng, D, false, ctx->stream);
+            for (int j = 0; j < 4 && tl; j++)
+                pnp::k_pad_col(dst[kTableField[j]], dst[kTableField[j]], tl, D, true, ctx->stream);
+        }
+        for (int j = 0; j < 4; j++) {
+            ctx->pk_owned[kSigmaField[j]] = std::move(sig[j]);
+            dst[kSigmaField[j]] = ctx->pk_owned[kSigmaField[j]].u64();
+        }
+        lap(t_up);
+        // row values -> coefficients (the tables stay columns: ProverKeyC.table1..4)
+        for (int f = 0; f < 44; f++)
+            if (dst[f] && kPkKinds[f] != kTable) pnp::ntt_run(ctx->ntt, dst[f], lg, true, false, ctx->stream);
+        lap(t_intt);
+        pk_derive_from_coeffs(ctx, dev, D);
+        lap(t_derive);
+        if (vk) {
+            vk->n = D;
+            PNP_HIP(hipMemcpyAsync(vk->g, ctx->ck_dev, 96, hipMemcpyDeviceToHost, ctx->stream));
+            const uint64_t *const *res = reinterpret_cast<const uint64_t *const *>(&ctx->pk_dev);
+            pnp::DevBuf tabc[4];
+            std::vector<const uint64_t *> sc;
+            std::vector<CommitmentC *> oc;
+            uint64_t one[6];
+            to_u64_limbs(Fq::one(), one);
+            for (int k = 0; k < PNP_VK_POLYS; k++) {
+                const int f = kVkField[k];
+                const uint64_t *p = res[f];
+                // (a mandatory selector or a table may be all zero too)
+                if (p && !pnp::k_any_nonzero(p, 4 * D, ctx->scratch_b, ctx->stream)) p = nullptr;
+                if (p && kPkKinds[f] == kTable) {
+                    pnp::DevBuf &t = tabc[f - kTableField[0]];
+                    t.alloc(32 * D);
+                    PNP_HIP(hipMemcpyAsync(t.p, p, 32 * D, hipMemcpyDeviceToDevice, ctx->stream));
+                    pnp::ntt_run(ctx->ntt, t.u64(), lg, true, false, ctx->stream);
+                    p = t.u64();
+                }
+                if (!p) {  // the zero polynomial
+                    memset(vk->polys[k].x, 0, 48);
+                    memcpy(vk->polys[k].y, one, 48);
+                    continue;
+                }
+                sc.push_back(p);
+                oc.push_back(&vk->polys[k]);
+            }
+            for (size_t b = 0; b < sc.size(); b += 8)
+                pnp::commit_affine_batch(ctx, sc.data() + b, (int)std::min<size_t>(8, sc.size() - b), D, oc.data() + b);
+            lap(t_vk);
+        }
+        ctx->stages.push_back({"pre_upload", t_up});
+        ctx->stages.push_back({"pre_permutation", t_perm});
+        ctx->stages.push_back({"pre_intt", t_intt});
+        ctx->stages.push_back({"pre_derive", t_derive});
+        ctx->stages.push_back({"pre_vk", t_vk});
+        ctx->stages.push_back({"pre_h2d_bytes", h2d_bytes});
     });
 }
 

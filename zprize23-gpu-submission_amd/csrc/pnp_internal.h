@@ -295,6 +295,23 @@ void k_coset_blocks(uint32_t lg_n, int m0, int nb, uint64_t *lin, uint64_t *lin3
 // array holding blocks m0 .. m0 + nb - 1 (zero when its block is not held)
 void k_gather_blocks(const uint64_t *blk, uint32_t lg_n, int m0, int nb, const uint64_t *d_idx, uint32_t cnt,
                      uint64_t *d_out, hipStream_t s);
+// ---- circuit preprocessing (preprocess.hip) ----
+// slots (4 row + wire) one workgroup of the permutation's radix sort ranks
+constexpr uint32_t PNP_SIGMA_TILE = 4096;
+struct WireSigmaStats {
+    int passes = 0;    // 8-bit digit passes the sort ran
+    double bytes = 0;  // what the kernels must move (keys, slot ids, next)
+};
+uint64_t wire_sigma_scratch_bytes(uint64_t n_gates);
+// the copy permutation of a wire map: d_next[j D + i] = j' D + i' (4 D u32)
+// and the sigma columns K_j' w^i' (D Montgomery Fr each; nullptr = not
+// wanted); returns the first slot 4 row + wire whose id is >= n_vars, ~0 when
+// there is none.  Synchronous; scratch grows to wire_sigma_scratch_bytes
+uint64_t wire_sigma(NttTables &ntt, const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, uint32_t lg,
+                    uint32_t *d_next, uint64_t *const d_sigma[4], DevBuf &scratch, hipStream_t s,
+                    WireSigmaStats *stats = nullptr);
+// dst[i] = src[i], i < n; then src[0] (first) or zero up to D; dst == src pads in place
+void k_pad_col(uint64_t *dst, const uint64_t *src, uint64_t n, uint64_t D, bool first, hipStream_t s);
 void k_synth_merkle(int height, const uint64_t *pc_mont_host, const uint64_t *leaves, const uint64_t *blind,
                     uint64_t *nodes, uint64_t *const w[4], uint64_t *const sel[9], uint64_t *const sigma[4],
                     uint64_t n, hipStream_t s);

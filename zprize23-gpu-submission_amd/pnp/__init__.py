@@ -36,7 +36,8 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_synth_random_fr", "pnp_synth_srs", "pnp_synth_coset_consts", "pnp_synth_circuit",
            "pnp_synth_merkle", "pnp_load_commit_key_strided", "pnp_proof_infinity_mask",
            "pnp_set_exchange_v", "pnp_commit_segments", "pnp_hbm_usage",
-           "pnp_ctx_stream", "pnp_set_exchange_ordered", "pnp_v1_context")
+           "pnp_ctx_stream", "pnp_set_exchange_ordered", "pnp_v1_context",
+           "pnp_preprocess", "pnp_wire_sigma")
 
 
 # int allgather(void *user, uint64_t bytes_per_rank) — pnp_set_msm_shard
@@ -78,6 +79,8 @@ def load(path: str = LIB_PATH):
     lib.pnp_load_prover_key.argtypes = [vp, C.POINTER(abi.ProverKeyC), u64, i32]
     lib.pnp_load_prover_key_coeffs.argtypes = [vp, C.POINTER(abi.ProverKeyC), u64, i32]
     lib.pnp_load_commit_key.argtypes = [vp, C.POINTER(abi.CommitKeyC), u64, i32]
+    lib.pnp_preprocess.argtypes = [vp, C.POINTER(abi.CircuitDesc), i32, C.POINTER(abi.VerifierKey)]
+    lib.pnp_wire_sigma.argtypes = [vp, C.c_void_p * 4, u64, u64, C.c_uint32, vp, C.POINTER(C.c_void_p * 4)]
     lib.pnp_prove.argtypes = [vp, C.POINTER(abi.CircuitC), i32, C.POINTER(abi.ProofC)]
     lib.pnp_prove_ex.argtypes = [vp, C.POINTER(abi.CircuitC), i32, u64, vp, vp, C.c_char_p,
                                  C.POINTER(abi.ProofC)]
@@ -168,6 +171,24 @@ class Context:
         *_evals fields may be NULL, an absent optional selector is NULL)."""
         check(self.lib.pnp_load_prover_key_coeffs(self.h, C.byref(pk), domain, int(device_ptrs)),
               "pnp_load_prover_key_coeffs")
+
+    def preprocess(self, desc: abi.CircuitDesc, device_ptrs: bool, want_vk: bool = False):
+        """pnp_preprocess: the resident prover key from the circuit's selector
+        columns, wire map and tables (sigmas built on the GPU); returns the
+        abi.VerifierKey when want_vk (needs the commit key loaded), else None."""
+        vk = abi.VerifierKey() if want_vk else None
+        check(self.lib.pnp_preprocess(self.h, C.byref(desc), int(device_ptrs), C.byref(vk) if want_vk else None),
+              "pnp_preprocess")
+        return vk
+
+    def wire_sigma(self, var, n_gates: int, n_vars: int, lg_n: int, next_addr: int = 0, sigma=None):
+        """pnp_wire_sigma: var = 4 HBM addresses of u32 ids; next_addr = HBM
+        address of 4 * 2^lg_n u32 (0: not wanted); sigma = 4 HBM addresses of
+        2^lg_n Fr (None, or single zeros: not wanted)."""
+        V = (C.c_void_p * 4)(*var)
+        S = (C.c_void_p * 4)(*[a or None for a in sigma]) if sigma is not None else None
+        check(self.lib.pnp_wire_sigma(self.h, V, n_gates, n_vars, lg_n, C.c_void_p(next_addr or None),
+                                      C.byref(S) if S is not None else None), "pnp_wire_sigma")
 
     def load_commit_key(self, ck: abi.CommitKeyC, n_points: int, device_ptrs: bool):
         check(self.lib.pnp_load_commit_key(self.h, C.byref(ck), n_points, int(device_ptrs)),

@@ -93,6 +93,35 @@ class AffineLayout(C.Structure):
 # (x: Fp384, y: Fp384, infinity: bool, 7 bytes of padding)
 ARK_G1_AFFINE = AffineLayout(stride=104, x_off=0, y_off=48, inf_off=96)
 
+U32P = C.POINTER(C.c_uint32)
+
+# pnp_verifier_key.polys, in order (the oracle's or_verifier_key)
+VK_POLYS = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_hl", "q_hr", "q_h4", "q_arith",
+            "range_selector", "logic_selector", "fixed_group_add_selector",
+            "variable_group_add_selector", "left_sigma", "right_sigma", "out_sigma",
+            "fourth_sigma", "q_lookup", "table1", "table2", "table3", "table4")
+# pnp_circuit_desc.sel, in order
+DESC_SELECTORS = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_hl", "q_hr", "q_h4", "q_arith",
+                  "range_selector", "logic_selector", "fixed_group_add_selector",
+                  "variable_group_add_selector", "q_lookup")
+
+
+class VerifierKey(C.Structure):
+    """pnp_verifier_key: the domain size, SRS_0 and the 23 commitments of the
+    preprocessed polynomials (VK_POLYS order); 1 + 12 + 23 * 12 u64."""
+    _fields_ = [("n", C.c_uint64), ("g", C.c_uint64 * 12), ("polys", CommitmentC * len(VK_POLYS))]
+
+
+class CircuitDesc(C.Structure):
+    """pnp_circuit_desc: what a composer holds.  var: 4 x n_gates u32 variable
+    ids (left, right, out, fourth); sel: DESC_SELECTORS row values (n_gates
+    Montgomery Fr each, NULL = a zero column); table: 4 x lookup_len Fr."""
+    _fields_ = [("n_gates", C.c_uint64), ("n_vars", C.c_uint64), ("lookup_len", C.c_uint64),
+                ("var", U32P * 4), ("sel", U64P * len(DESC_SELECTORS)), ("table", U64P * 4)]
+
+
+assert C.sizeof(VerifierKey) == 8 + 96 + 23 * 96
+assert C.sizeof(CircuitDesc) == 3 * 8 + (4 + 15 + 4) * 8
 assert C.sizeof(ProofC) == 2656
 assert C.sizeof(CircuitC) == 72
 assert C.sizeof(ProverKeyC) == 44 * 8
