@@ -338,6 +338,32 @@ typedef struct {
  * kernels had to move, and pre_h2d_bytes, what crossed PCIe. */
 int pnp_preprocess(pnp_ctx *ctx, const pnp_circuit_desc *c, int device_ptrs, pnp_verifier_key *vk /* may be NULL */);
 
+/* The resident wire map.  pnp_preprocess keeps a device copy of the four id
+ * columns it was given (4 n_gates u32) and of n_vars, owned by the context and
+ * counted in pnp_hbm_usage out[0], with the row values of q_lookup on the
+ * domain (D Montgomery Fr, a forward transform of the resident coefficients;
+ * nothing for the zero polynomial): what pnp_prove_assignment needs to build
+ * the witness columns itself.  The map is replaced by the next pnp_preprocess
+ * and dropped by pnp_load_prover_key / pnp_load_prover_key_coeffs.
+ *
+ * pnp_load_wire_map gives a key loaded by one of those two its map.  var[j]:
+ * n_gates variable ids of wire j (host, or HBM with device_ptrs; copied, not
+ * adopted), each < n_vars, n_gates <= the key's domain size D.  The map must
+ * be the key's: its sigma columns, built by the permutation kernels of
+ * pnp_wire_sigma, must equal the forward transforms of the four resident
+ * sigma coefficient arrays.  Synchronous; the scratch (the sort's, next, four
+ * columns of D Fr) is released before it returns.
+ * Errors (the key keeps proving; after a bad id or a sigma mismatch NO map is
+ * resident, an earlier one included):
+ *   PNP_E_ARG    a NULL column, n_gates = 0 or > D, a variable id >= n_vars
+ *                (wire and row in pnp_last_error), a sigma that differs from
+ *                the key's (the first wire and row, in (row, wire) order, in
+ *                pnp_last_error), or a context sharded over several ranks
+ *                (as pnp_preprocess)
+ *   PNP_E_NOKEY  no prover key loaded */
+int pnp_load_wire_map(pnp_ctx *ctx, const uint32_t *const var[4], uint64_t n_gates, uint64_t n_vars,
+                      int device_ptrs);
+
 /* The commit key straight from arkworks' memory, without the per-proof
  * conversion prove_pnp does today (prover.rs:700-711 rebuilds (x, y) tuples
  * of all 2^24+1 SRS points on every call): `points` = the address of
@@ -383,6 +409,30 @@ int pnp_prove(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out);
  * pnp_prove's. */
 int pnp_prove_ex(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t n_pi,
                  const uint64_t *pi_pos, const uint64_t *pi_canon, const char *label, ProofC *out);
+
+/* Prove from a variable assignment over the resident wire map (pnp_preprocess
+ * or pnp_load_wire_map first): the host hands over one value per variable
+ * instead of expanding them into four columns through the wire map it gave
+ * the library a moment earlier (prover.rs:197-216: four passes of
+ * variables[&w_x[i]] over a HashMap) — 32 n_vars bytes per proof, not
+ * 5 * 32 * n_gates.  values: n_vars Montgomery Fr indexed by variable id, in
+ * host memory (one staged upload) or, with device_ptrs, in HBM (16-byte
+ * aligned; read in place).  n_gates and the domain are the ones the map and
+ * the key were loaded with; q_lookup is the key's.  Public inputs and label
+ * exactly as pnp_prove_ex.  The columns w_j[i] = values[var_j[i]], zero from
+ * row n_gates on, are written by one gather launch into the prover's padded
+ * witness buffers; from round 1 on the prover is pnp_prove_ex's, and the proof
+ * is byte for byte the one pnp_prove_ex returns for those columns and the
+ * key's q_lookup rows.  The assignment is not checked to satisfy the circuit
+ * (an unsatisfied one proves like unsatisfied columns do).  Single GPU.
+ * Afterwards pnp_last_stage_times carries one extra entry, a count:
+ * inputs_h2d_bytes = 32 n_vars for host values, 0 for HBM values; the gather
+ * is timed as "gather_witness" (pnp_kernel_timing).
+ *   PNP_E_NOKEY  no keys, or no wire map resident ("no wire map")
+ *   PNP_E_ARG    n_vars differs from the map's; the errors of pnp_prove_ex */
+int pnp_prove_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, int device_ptrs,
+                         uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
+                         const char *label, ProofC *out);
 
 /* Per-stage wall-clock (ms) of the last pnp_prove, for the bench/profiles.
  * Writes up to `cap` doubles and their names; returns the stage count. */
@@ -540,6 +590,19 @@ int pnp_commit_segments(pnp_ctx *ctx, const uint64_t *d_points, uint64_t n_point
  * (the outputs are then unspecified). */
 int pnp_wire_sigma(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars,
                    uint32_t lg_n, uint32_t *d_next, uint64_t *const d_sigma[4]);
+
+/* Extension (operator form of pnp_prove_assignment's gather, assignment.hip):
+ * the witness columns of a variable assignment on the domain D = 2^lg_n >=
+ * n_gates (lg_n <= 25), in one launch: d_w[j][i] = d_values[d_var[j][i]] for
+ * i < n_gates and zero for n_gates <= i < D (every row of the four outputs is
+ * written).  d_var[j]: n_gates u32 ids; d_values: n_vars Montgomery Fr;
+ * d_w[j]: D Fr; all HBM pointers, the Fr arrays 16-byte aligned.  The ids are
+ * trusted to be < n_vars (the loaders validate their maps); one that is not
+ * reads as zero, never outside d_values.  Asynchronous on the context stream.
+ * PNP_E_ARG for n_gates = 0, n_gates > 2^lg_n, lg_n > 25, a NULL or misaligned
+ * pointer. */
+int pnp_gather_witness(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates,
+                       const uint64_t *d_values, uint64_t n_vars, uint32_t lg_n, uint64_t *const d_w[4]);
 
 /* evaluate (function.cu:162-173): sum_i c_i x^i; x and result Montgomery,
  * host-side scalars.  Synchronous. */

@@ -1167,6 +1167,7 @@ int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int devi
         tables_wait(ctx);  // a background build reads the key being replaced: let it finish
         PNP_HIP(hipSetDevice(ctx->device));
         ctx->pk_loaded = false;
+        ctx->wire_map_drop();  // (the map of the key being replaced)
         ctx->pk_gen++;  // derived groups (wires.hip) re-check sigma
         // device copies are kept across loads and reused when a field's size is
         // unchanged (the v1 symbol reloads every call: no hipMalloc / hipFree of
@@ -1336,6 +1337,7 @@ int pnp_load_prover_key_coeffs(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, i
         tables_wait(ctx);  // a background build reads the key being replaced: let it finish
         PNP_HIP(hipSetDevice(ctx->device));
         ctx->pk_loaded = false;
+        ctx->wire_map_drop();  // (the map of the key being replaced)
         ctx->pk_gen++;
         ctx->pk_owned.resize(44);
         ProverKeyC dev{};
@@ -1388,9 +1390,109 @@ bool bad_variable(uint64_t slot, uint64_t n_vars) {
     return true;
 }
 
+// the caller's four id columns (host or HBM) as one array the library owns:
+// column j at u32 offset j * ng
+void wire_map_copy(pnp_ctx *ctx, const uint32_t *const var[4], uint64_t ng, int device_ptrs, pnp::DevBuf &out) {
+    out.alloc(16 * ng);
+    std::vector<H2D> up;
+    for (int j = 0; j < 4; j++) {
+        uint32_t *d = static_cast<uint32_t *>(out.p) + j * ng;
+        if (device_ptrs) PNP_HIP(hipMemcpyAsync(d, var[j], 4 * ng, hipMemcpyDeviceToDevice, ctx->stream));
+        else up.push_back({d, var[j], 4 * ng});
+    }
+    if (!up.empty()) h2d_batch(ctx, up);
+}
+
+// `var` (wire_map_copy) becomes the resident wire map of the resident key, and
+// the q_lookup row values are derived from the key's coefficients (a forward
+// transform; nothing is kept for the zero polynomial)
+void wire_map_adopt(pnp_ctx *ctx, pnp::DevBuf &var, uint64_t ng, uint64_t n_vars) {
+    ctx->wire_map_drop();
+    const uint64_t D = ctx->pk_n;
+    if (ctx->pk_dev.q_lookup_coeffs) {
+        uint32_t lg = 0;
+        while ((1ULL << lg) < D) lg++;
+        ctx->wm_qlk.alloc(32 * D);
+        PNP_HIP(hipMemcpyAsync(ctx->wm_qlk.p, ctx->pk_dev.q_lookup_coeffs, 32 * D, hipMemcpyDeviceToDevice,
+                               ctx->stream));
+        pnp::ntt_run(ctx->ntt, ctx->wm_qlk.u64(), lg, false, false, ctx->stream);  // (as pk_sigma_domain)
+        PNP_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->wm_var = std::move(var);
+    ctx->wm_gates = ng;
+    ctx->wm_vars = n_vars;
+    ctx->wm_loaded = true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pnp_load_wire_map(pnp_ctx *ctx, const uint32_t *const var[4], uint64_t n_gates, uint64_t n_vars,
+                      int device_ptrs) {
+    if (!ctx || !var || !var[0] || !var[1] || !var[2] || !var[3] || n_gates == 0) return PNP_E_ARG;
+    if (!ctx->pk_loaded) {
+        set_error("load wire map: prover key not loaded");
+        return PNP_E_NOKEY;
+    }
+    if (ctx->msm.world > 1) {
+        set_error("load wire map: the context is sharded over %d ranks (multi-rank wire maps are not supported)",
+                  ctx->msm.world);
+        return PNP_E_ARG;
+    }
+    const uint64_t D = ctx->pk_n;
+    if (n_gates > D) {
+        set_error("load wire map: %llu gates, the resident key's domain has %llu rows", (unsigned long long)n_gates,
+                  (unsigned long long)D);
+        return PNP_E_ARG;
+    }
+    PNP_TRY({
+        tables_wait(ctx);  // (the NTT tables are shared with a background build)
+        PNP_HIP(hipSetDevice(ctx->device));
+        ctx->wire_map_drop();  // a refused map leaves none resident
+        uint32_t lg = 0;
+        while ((1ULL << lg) < D) lg++;
+        pnp::DevBuf ids;
+        wire_map_copy(ctx, var, n_gates, device_ptrs, ids);
+        {
+            // the sigmas of this map must be the resident key's (the forward
+            // transforms of its sigma coefficients, kept since the key load)
+            pnp::DevBuf sig[4], next(16 * D), sort, first;
+            const uint32_t *base = static_cast<const uint32_t *>(ids.p);
+            const uint32_t *dvar[4] = {base, base + n_gates, base + 2 * n_gates, base + 3 * n_gates};
+            uint64_t *dsig[4];
+            const uint64_t *csig[4], *ksig[4];
+            for (int j = 0; j < 4; j++) {
+                sig[j].alloc(32 * D);
+                csig[j] = dsig[j] = sig[j].u64();
+                ksig[j] = ctx->pk_sigma_n[j].u64();
+            }
+            const uint64_t bad = pnp::wire_sigma(ctx->ntt, dvar, n_gates, n_vars, lg, static_cast<uint32_t *>(next.p),
+                                                 dsig, sort, ctx->stream);
+            if (bad_variable(bad, n_vars)) throw Error(PNP_E_ARG);
+            const uint64_t diff = pnp::k_first_diff4(csig, ksig, lg, first, ctx->stream);
+            if (diff != ~0ULL) {
+                set_error("load wire map: the map's sigma differs from the resident key's in wire %d of row %llu",
+                          (int)(diff & 3), (unsigned long long)(diff >> 2));
+                throw Error(PNP_E_ARG);
+            }
+        }  // (the scratch is released here)
+        wire_map_adopt(ctx, ids, n_gates, n_vars);
+    });
+}
+
+int pnp_gather_witness(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates, const uint64_t *d_values,
+                       uint64_t n_vars, uint32_t lg_n, uint64_t *const d_w[4]) {
+    if (!ctx || !d_var || !d_w || !d_values || n_gates == 0 || lg_n > 25 || n_gates > (1ULL << lg_n))
+        return PNP_E_ARG;
+    for (int j = 0; j < 4; j++)
+        if (!d_var[j] || !d_w[j] || ((uintptr_t)d_w[j] & 15) || ((uintptr_t)d_var[j] & 3)) return PNP_E_ARG;
+    if ((uintptr_t)d_values & 15) return PNP_E_ARG;  // (field elements are read and written 16 bytes at a time)
+    PNP_TRY({
+        PNP_HIP(hipSetDevice(ctx->device));
+        pnp::k_gather_witness(d_var, n_gates, d_values, n_vars, lg_n, d_w, ctx->stream);
+    });
+}
 
 int pnp_wire_sigma(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, uint32_t lg_n,
                    uint32_t *d_next, uint64_t *const d_sigma[4]) {
@@ -1460,21 +1562,15 @@ int pnp_preprocess(pnp_ctx *ctx, const pnp_circuit_desc *c, int device_ptrs, pnp
             t0 = t1;
         };
         // the permutation first, into scratch: a bad id is an argument error
-        pnp::DevBuf sig[4];
+        // (the ids are copied whichever side they come from: the copy becomes
+        // the resident wire map of the new key)
+        pnp::DevBuf sig[4], vars;
         {
-            pnp::DevBuf vars, next(16 * D), sort;
-            const uint32_t *dvar[4] = {c->var[0], c->var[1], c->var[2], c->var[3]};
-            if (!device_ptrs) {
-                vars.alloc(16 * ng);
-                std::vector<H2D> up;
-                for (int j = 0; j < 4; j++) {
-                    uint32_t *d = static_cast<uint32_t *>(vars.p) + j * ng;
-                    up.push_back({d, c->var[j], 4 * ng});
-                    dvar[j] = d;
-                }
-                h2d_batch(ctx, up);
-                h2d_bytes += 16.0 * ng;
-            }
+            pnp::DevBuf next(16 * D), sort;
+            wire_map_copy(ctx, c->var, ng, device_ptrs, vars);
+            if (!device_ptrs) h2d_bytes += 16.0 * ng;
+            const uint32_t *vbase = static_cast<const uint32_t *>(vars.p);
+            const uint32_t *dvar[4] = {vbase, vbase + ng, vbase + 2 * ng, vbase + 3 * ng};
             lap(t_up);
             uint64_t *dsig[4];
             for (int j = 0; j < 4; j++) {
@@ -1487,9 +1583,10 @@ int pnp_preprocess(pnp_ctx *ctx, const pnp_circuit_desc *c, int device_ptrs, pnp
             if (bad_variable(bad, c->n_vars)) throw Error(PNP_E_ARG);
             ctx->stages.clear();
             ctx->stages.push_back({"pre_permutation_bytes", st.bytes});
-        }  // (the sort scratch, the id copies and next are released here)
+        }  // (the sort scratch and next are released here)
         lap(t_perm);
-        // ---- the resident key is replaced from here on
+        // ---- the resident key is replaced from here on, and its wire map with it
+        ctx->wire_map_drop();
         ctx->pk_loaded = false;
         ctx->pk_gen++;
         ctx->pk_owned.resize(44);
@@ -1535,6 +1632,7 @@ int pnp_preprocess(pnp_ctx *ctx, const pnp_circuit_desc *c, int device_ptrs, pnp
             if (dst[f] && kPkKinds[f] != kTable) pnp::ntt_run(ctx->ntt, dst[f], lg, true, false, ctx->stream);
         lap(t_intt);
         pk_derive_from_coeffs(ctx, dev, D);
+        wire_map_adopt(ctx, vars, ng, c->n_vars);
         lap(t_derive);
         if (vk) {
             vk->n = D;
@@ -1704,6 +1802,28 @@ int pnp_prove_ex(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t n_p
     ProveOpts o{n_pi, pi_pos, pi_canon, label ? label : "Merkle tree"};
     try {
         return prove_impl(ctx, cs, device_ptrs, out, &o);
+    } catch (const Error &e) {
+        return e.code;
+    } catch (const std::exception &e) {
+        set_error("exception: %s", e.what());
+        return PNP_E_DEVICE;
+    } catch (...) {
+        set_error("unknown exception");
+        return PNP_E_DEVICE;
+    }
+}
+
+int pnp_prove_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, int device_ptrs, uint64_t n_pi,
+                         const uint64_t *pi_pos, const uint64_t *pi_canon, const char *label, ProofC *out) {
+    if (!ctx || !values || !out || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
+    if (device_ptrs && ((uintptr_t)values & 15)) {
+        set_error("prove assignment: HBM values must be 16-byte aligned");
+        return PNP_E_ARG;
+    }
+    ProveOpts o{n_pi, pi_pos, pi_canon, label ? label : "Merkle tree"};
+    Assignment a{values, n_vars};
+    try {
+        return prove_impl(ctx, nullptr, device_ptrs, out, &o, &a);
     } catch (const Error &e) {
         return e.code;
     } catch (const std::exception &e) {

@@ -58,6 +58,23 @@ struct pnp_ctx {
         auto it = pk_blk29.find(name);
         return it == pk_blk29.end() ? nullptr : it->second.u64();
     }
+    // ---- resident wire map (pnp_preprocess, pnp_load_wire_map) ----
+    // the composer's variable ids of the resident key's circuit: column j (wire
+    // j of every gate) at u32 offset j * wm_gates; pnp_prove_assignment
+    // gathers the witness through it (assignment.hip).  Replaced by the next
+    // preprocess, dropped by any other key load
+    bool wm_loaded = false;
+    uint64_t wm_gates = 0, wm_vars = 0;
+    pnp::DevBuf wm_var;
+    // the row values of q_lookup on the domain (pk_n Fr), from the resident
+    // coefficients when the map became resident; empty: the zero polynomial
+    pnp::DevBuf wm_qlk;
+    void wire_map_drop() {
+        wm_loaded = false;
+        wm_gates = wm_vars = 0;
+        wm_var.release();
+        wm_qlk.release();
+    }
     // ---- resident commit key ----
     bool ck_loaded = false;
     uint64_t ck_points = 0;
@@ -218,5 +235,16 @@ struct ProveOpts {
     const uint64_t *pi_pos, *pi_canon;
     const char *label;
 };
-int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt = nullptr);
+// the witness as a variable assignment over the resident wire map
+// (pnp_prove_assignment): n_vars Montgomery Fr by variable id, in host memory
+// or HBM as device_ptrs says
+struct Assignment {
+    const uint64_t *values;
+    uint64_t n_vars;
+};
+// The witness comes from the columns of `cs`, or, with `asg` (then cs is
+// nullptr and opt is given), from the assignment: the domain is the resident
+// key's, the gates and q_lookup rows the resident wire map's.
+int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt = nullptr,
+               const Assignment *asg = nullptr);
 }  // namespace pnp

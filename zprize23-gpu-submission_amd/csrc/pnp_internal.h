@@ -312,6 +312,15 @@ uint64_t wire_sigma(NttTables &ntt, const uint32_t *const d_var[4], uint64_t n_g
                     WireSigmaStats *stats = nullptr);
 // dst[i] = src[i], i < n; then src[0] (first) or zero up to D; dst == src pads in place
 void k_pad_col(uint64_t *dst, const uint64_t *src, uint64_t n, uint64_t D, bool first, hipStream_t s);
+// ---- the witness from a variable assignment (assignment.hip) ----
+// d_w[j][i] = d_values[d_var[j][i]] for i < n_gates, zero for n_gates <= i <
+// 2^lg: one launch over the 2^lg rows.  An id >= n_vars reads as zero.
+void k_gather_witness(const uint32_t *const d_var[4], uint64_t n_gates, const uint64_t *d_values, uint64_t n_vars,
+                      uint32_t lg, uint64_t *const d_w[4], hipStream_t s);
+// the first slot 4 row + wire at which the columns a[j] and b[j] (2^lg Fr
+// each) differ, ~0 when they are equal.  Synchronous; scratch: 8 bytes
+uint64_t k_first_diff4(const uint64_t *const a[4], const uint64_t *const b[4], uint32_t lg, DevBuf &scratch,
+                       hipStream_t s);
 void k_synth_merkle(int height, const uint64_t *pc_mont_host, const uint64_t *leaves, const uint64_t *blind,
                     uint64_t *nodes, uint64_t *const w[4], uint64_t *const sel[9], uint64_t *const sigma[4],
                     uint64_t n, hipStream_t s);

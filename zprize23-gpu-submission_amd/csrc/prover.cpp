@@ -110,15 +110,29 @@ void div_linear_range(pnp_ctx *ctx, uint64_t *const *d, const Fr *z, int K, uint
 
 }  // namespace
 
-int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt) {
+int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt,
+               const Assignment *asg) {
     if (!ctx->pk_loaded || !ctx->ck_loaded) {
         set_error("prover key / commit key not loaded");
         return PNP_E_NOKEY;
     }
+    if (asg) {
+        if (!ctx->wm_loaded) {
+            set_error("no wire map resident (pnp_preprocess or pnp_load_wire_map first)");
+            return PNP_E_NOKEY;
+        }
+        if (asg->n_vars != ctx->wm_vars) {
+            set_error("assignment of %llu variables, the resident wire map has %llu", (unsigned long long)asg->n_vars,
+                      (unsigned long long)ctx->wm_vars);
+            return PNP_E_ARG;
+        }
+    }
     memset(out, 0, sizeof *out);
     hipStream_t s = ctx->stream;
     PNP_HIP(hipSetDevice(ctx->device));
-    uint64_t bound = cs->n > cs->lookup_len ? cs->n : cs->lookup_len;
+    // the domain: the circuit's, which must be the key's; an assignment is
+    // proved on the key's (its wire map was loaded against it)
+    uint64_t bound = asg ? ctx->pk_n : cs->n > cs->lookup_len ? cs->n : cs->lookup_len;
     uint64_t n = 1;
     uint32_t lg = 0;
     while (n < bound) { n <<= 1; lg++; }
@@ -183,7 +197,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         ctx->hbm_checked = true;
     }
     ctx->msm.batch_seq = 0;  // the fixed-slot exchange keys its capacities by batch ordinal
-    const uint64_t N8 = 8 * n, ng = cs->n;
+    const uint64_t N8 = 8 * n, ng = asg ? ctx->wm_gates : cs->n;
     const ProverKeyC &pk = ctx->pk_dev;
     Timer tm(ctx);
     auto &nt = ctx->ntt;
@@ -250,21 +264,50 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     };
 
     // ---------------- inputs: padded witness evaluations (pad_poly)
+    // from the caller's columns (copies and zero fills), or gathered from its
+    // variable assignment through the resident wire map (assignment.hip: one
+    // launch writes the columns and their padding).  qlk: the q_lookup rows,
+    // the first qlk_rows of them read (none: a zero column)
     uint64_t *wsc[4], *wpoly[4];
-    const uint64_t *wsrc[4] = {cs->w_l, cs->w_r, cs->w_o, cs->w_4};
-    std::vector<H2D> up;  // a host witness: staged uploads (abi.cpp h2d_batch)
     for (int j = 0; j < 4; j++) {
         wsc[j] = ctx->buf("wsc" + std::to_string(j), n);
         wpoly[j] = ctx->buf("wpoly" + std::to_string(j), n);
-        if (device_ptrs) PNP_HIP(hipMemcpyAsync(wsc[j], wsrc[j], 32 * ng, hipMemcpyDeviceToDevice, s));
-        else up.push_back({wsc[j], wsrc[j], 32 * ng});
-        if (n > ng) PNP_HIP(hipMemsetAsync(wsc[j] + 4 * ng, 0, 32 * (n - ng), s));
     }
-    uint64_t *qlk = ctx->buf("qlk", n);
-    if (device_ptrs) PNP_HIP(hipMemcpyAsync(qlk, cs->q_lookup, 32 * ng, hipMemcpyDeviceToDevice, s));
-    else up.push_back({qlk, cs->q_lookup, 32 * ng});
-    if (!up.empty()) h2d_batch(ctx, up);
-    alg(4.0 * (2 * ng + (n - ng)) + 2.0 * ng);
+    const uint64_t *qlk = nullptr;
+    uint64_t qlk_rows = ng;
+    double inputs_h2d = 0;
+    if (asg) {
+        const uint64_t *vals = asg->values;
+        if (!device_ptrs) {  // one staged upload (abi.cpp h2d_batch)
+            uint64_t *dv = ctx->buf("asg_values", asg->n_vars);
+            h2d_batch(ctx, {{dv, vals, 32 * asg->n_vars}});
+            inputs_h2d = 32.0 * asg->n_vars;
+            vals = dv;
+        }
+        const uint32_t *var = static_cast<const uint32_t *>(ctx->wm_var.p);
+        const uint32_t *dvar[4] = {var, var + ng, var + 2 * ng, var + 3 * ng};
+        hipEvent_t e0 = nullptr;
+        ctx->ktimer.begin("gather_witness", s, e0);
+        k_gather_witness(dvar, ng, vals, asg->n_vars, lg, wsc, s);
+        ctx->ktimer.end("gather_witness", s, e0, 16.0 * ng + 4.0 * 32 * ng + 4.0 * 32 * n);
+        if (ctx->wm_qlk.p) qlk = ctx->wm_qlk.u64();
+        else qlk_rows = 0;
+        alg(4.0 * (ng / 8.0 + ng + n));  // ids, gathered values, padded columns
+    } else {
+        const uint64_t *wsrc[4] = {cs->w_l, cs->w_r, cs->w_o, cs->w_4};
+        std::vector<H2D> up;  // a host witness: staged uploads (abi.cpp h2d_batch)
+        for (int j = 0; j < 4; j++) {
+            if (device_ptrs) PNP_HIP(hipMemcpyAsync(wsc[j], wsrc[j], 32 * ng, hipMemcpyDeviceToDevice, s));
+            else up.push_back({wsc[j], wsrc[j], 32 * ng});
+            if (n > ng) PNP_HIP(hipMemsetAsync(wsc[j] + 4 * ng, 0, 32 * (n - ng), s));
+        }
+        uint64_t *q = ctx->buf("qlk", n);
+        if (device_ptrs) PNP_HIP(hipMemcpyAsync(q, cs->q_lookup, 32 * ng, hipMemcpyDeviceToDevice, s));
+        else up.push_back({q, cs->q_lookup, 32 * ng});
+        if (!up.empty()) h2d_batch(ctx, up);
+        qlk = q;
+        alg(4.0 * (2 * ng + (n - ng)) + 2.0 * ng);
+    }
     tm.mark("inputs");
 
     Transcript tr(opt ? opt->label : "Merkle tree");
@@ -322,7 +365,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     const bool table_zero = !k_any_nonzero(tc, 4 * n, ctx->scratch_b, s);
     uint64_t *fc = ctx->buf("fc", n), *f_poly = ctx->buf("f_poly", n);
     const uint64_t *wconst[4] = {wsc[0], wsc[1], wsc[2], wsc[3]};
-    k_query_f(fc, qlk, ng, wconst, tc, zeta, n, s);
+    k_query_f(fc, qlk, qlk_rows, wconst, tc, zeta, n, s);
     const bool f_zero = !k_any_nonzero(fc, 4 * n, ctx->scratch_b, s);
     alg(5.0 * n + n + ng + n + n);  // compress, its check, query (q_lookup in, f out), its check
     // (zero f / table: their polynomials are never read)
@@ -1060,6 +1103,8 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     }
     // the tables this proof went without: built in the background from now
     if (bg_mode && ctx->defer_now && ctx->tables_wanted) tables_start_background(ctx, n);
+    // a count in the same list (an assignment proof only): what its witness moved over PCIe
+    if (asg) ctx->stages.emplace_back("inputs_h2d_bytes", inputs_h2d);
     return PNP_OK;
 }
 

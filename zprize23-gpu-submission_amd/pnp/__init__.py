@@ -37,7 +37,8 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_synth_merkle", "pnp_load_commit_key_strided", "pnp_proof_infinity_mask",
            "pnp_set_exchange_v", "pnp_commit_segments", "pnp_hbm_usage",
            "pnp_ctx_stream", "pnp_set_exchange_ordered", "pnp_v1_context",
-           "pnp_preprocess", "pnp_wire_sigma")
+           "pnp_preprocess", "pnp_wire_sigma",
+           "pnp_load_wire_map", "pnp_gather_witness", "pnp_prove_assignment")
 
 
 # int allgather(void *user, uint64_t bytes_per_rank) — pnp_set_msm_shard
@@ -84,6 +85,8 @@ def load(path: str = LIB_PATH):
     lib.pnp_prove.argtypes = [vp, C.POINTER(abi.CircuitC), i32, C.POINTER(abi.ProofC)]
     lib.pnp_prove_ex.argtypes = [vp, C.POINTER(abi.CircuitC), i32, u64, vp, vp, C.c_char_p,
                                  C.POINTER(abi.ProofC)]
+    for name, argtypes in abi.ASSIGNMENT_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes
     lib.pnp_last_stage_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_char_p), i32]
     lib.pnp_kernel_timing.argtypes = [vp, i32]
     lib.pnp_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -219,6 +222,28 @@ class Context:
                                     C.byref(out)), "pnp_prove_ex")
         return out
 
+    def load_wire_map(self, var, n_gates: int, n_vars: int, device_ptrs: bool):
+        """pnp_load_wire_map: var = 4 addresses (host, or HBM with device_ptrs)
+        of n_gates u32 variable ids; the map must be the resident key's."""
+        V = (C.c_void_p * 4)(*var)
+        check(self.lib.pnp_load_wire_map(self.h, V, n_gates, n_vars, int(device_ptrs)), "pnp_load_wire_map")
+
+    def prove_assignment(self, values: int, n_vars: int, device_ptrs: bool, pis,
+                         label: bytes = b"Merkle tree") -> abi.ProofC:
+        """pnp_prove_assignment: values = address (host, or HBM with
+        device_ptrs) of n_vars Montgomery Fr by variable id; pis as prove_ex."""
+        k = len(pis)
+        pos = (C.c_uint64 * max(k, 1))(*[p for p, _ in pis])
+        vals = (C.c_uint64 * max(4 * k, 1))()
+        for i, (_, v) in enumerate(pis):
+            for j in range(4):
+                vals[4 * i + j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+        out = abi.ProofC()
+        check(self.lib.pnp_prove_assignment(self.h, C.c_void_p(values), n_vars, int(device_ptrs), k,
+                                            C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p), label,
+                                            C.byref(out)), "pnp_prove_assignment")
+        return out
+
     def stage_times(self):
         cap = 64
         ms = (C.c_double * cap)()
@@ -320,6 +345,14 @@ class Context:
         check(self.lib.pnp_commit_segments(self.h, C.c_void_p(points), n_points, B, offs, sc, n, out),
               "pnp_commit_segments")
         return list(out)
+
+    def gather_witness(self, var, n_gates: int, values: int, n_vars: int, lg_n: int, w):
+        """pnp_gather_witness: var = 4 HBM addresses of n_gates u32 ids, values
+        = HBM address of n_vars Fr, w = 4 HBM addresses of 2^lg_n Fr (out)."""
+        V = (C.c_void_p * 4)(*[a or None for a in var])
+        W = (C.c_void_p * 4)(*[a or None for a in w])
+        check(self.lib.pnp_gather_witness(self.h, V, n_gates, C.c_void_p(values or None), n_vars, lg_n, W),
+              "pnp_gather_witness")
 
     def poly_eval(self, addr: int, n: int, x_limbs):
         x = (C.c_uint64 * 4)(*x_limbs)

@@ -120,6 +120,19 @@ class CircuitDesc(C.Structure):
                 ("var", U32P * 4), ("sel", U64P * len(DESC_SELECTORS)), ("table", U64P * 4)]
 
 
+# Proving from a variable assignment over the resident wire map: the ctypes
+# argument lists of the three entry points (pnp.load() installs them).
+#   pnp_load_wire_map(ctx, var[4], n_gates, n_vars, device_ptrs)
+#   pnp_gather_witness(ctx, d_var[4], n_gates, d_values, n_vars, lg_n, d_w[4])
+#   pnp_prove_assignment(ctx, values, n_vars, device_ptrs, n_pi, pi_pos, pi_canon, label, out)
+ASSIGNMENT_ARGTYPES = {
+    "pnp_load_wire_map": [C.c_void_p, C.c_void_p * 4, C.c_uint64, C.c_uint64, C.c_int],
+    "pnp_gather_witness": [C.c_void_p, C.c_void_p * 4, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                           C.c_void_p * 4],
+    "pnp_prove_assignment": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                             C.c_char_p, C.POINTER(ProofC)],
+}
+
 assert C.sizeof(VerifierKey) == 8 + 96 + 23 * 96
 assert C.sizeof(CircuitDesc) == 3 * 8 + (4 + 15 + 4) * 8
 assert C.sizeof(ProofC) == 2656
