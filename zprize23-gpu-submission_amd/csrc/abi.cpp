@@ -347,9 +347,7 @@ const uint64_t *lagrange_table(pnp_ctx *ctx, uint64_t n) {
             ctx->lag_table.release();
             ctx->lag_n = 0;
             ctx->lag_points.alloc(n * 96);
-            uint32_t lg = 0;
-            while ((1ULL << lg) < n) lg++;
-            ctx->lag_ok = srs_lagrange(ctx->ck_dev, n, inverse(root_of_unity(lg)), inverse(fr_from_u64(n)),
+            ctx->lag_ok = srs_lagrange(ctx->ck_dev, n, inverse(root_of_unity(log2_exact(n))), inverse(fr_from_u64(n)),
                                        ctx->lag_points.u64(), tables_stream(ctx));
             ctx->lag_n = n;
             if (!ctx->lag_ok) ctx->lag_points.release();
@@ -405,9 +403,9 @@ HbmPlan hbm_plan(pnp_ctx *ctx, uint64_t n) {
     const bool full = wk.full_table();
     const uint64_t per = (n + world - 1) / world;  // this rank's point range (at most)
     const uint64_t n_tab = full ? n : per;
-    const bool dist = ctx->pk_nb < 8;
-    const uint64_t len = dist ? per : n, NB = (uint64_t)ctx->pk_nb * n, N8 = 8 * n;
-    const bool lookups = !ctx->pk_qlookup_zero;
+    const bool dist = ctx->key.nb < 8;
+    const uint64_t len = dist ? per : n, NB = (uint64_t)ctx->key.nb * n, N8 = 8 * n;
+    const bool lookups = !ctx->key.qlookup_zero();
     // per-proof buffers (prover.cpp ctx->buf): 21 of n always (wires, their
     // coefficients, the lookup / grand-product vectors), the PI and L1
     // polynomials when not in closed form; 11 of the coefficient range (t
@@ -415,10 +413,10 @@ HbmPlan hbm_plan(pnp_ctx *ctx, uint64_t n) {
     // wire / z / z2 LDEs and t (7), the PI term's 1 / (x - w^pos), the lookup
     // LDEs, the L1 / PI LDEs when not in closed form; the batch-inverse /
     // scan scratch (about one vector of the longest length)
-    const bool closed = ctx->pk_std_coset;
+    const bool closed = ctx->key.std_coset;
     const uint64_t work = 32 * (21 * n + (closed ? 0 : 2 * n) + 11 * len +
                                 NB * (8 + (lookups ? 4 : 0) + (closed ? 0 : 2)) + std::max(n, NB) * 9 / 8);
-    const uint64_t work_held = map_bytes(ctx->work) + ctx->scratch_a.bytes + ctx->scratch_b.bytes + ctx->pk_pinv.bytes;
+    const uint64_t work_held = map_bytes(ctx->work) + ctx->scratch_a.bytes + ctx->scratch_b.bytes + ctx->key.pinv.bytes;
     // NTT tables: twiddles of n (both directions), the block twists (forward,
     // inverse, x32) of the 8n coset; with PNP_NTT29 their 2^261 forms
     static const bool ntt29 = [] {
@@ -495,7 +493,7 @@ void hbm_budget(pnp_ctx *ctx) {
         const uint64_t lim = strtoull(e, nullptr, 0), live = g_dev_live.load();
         budget = std::min<uint64_t>(budget, lim > live ? lim - live : 0);
     }
-    const HbmPlan p = hbm_plan(ctx, ctx->pk_n);
+    const HbmPlan p = hbm_plan(ctx, ctx->key.n);
     // each optional table with the largest build scratch among what is built
     const uint64_t base = p.mandatory + p.t_mand;
     const uint64_t with_lag = p.mandatory + p.lag + std::max(p.t_mand, p.t_lag);
@@ -538,7 +536,7 @@ void hbm_budget(pnp_ctx *ctx) {
     if (!ok) {
         set_error("HBM budget: rank %d of %d needs %.2f GiB more for a proof at n = %llu, %.2f GiB free to it "
                   "(%llu rank(s) on this rank's GPU; PNP_HBM_BUDGET=0 lets the allocations decide)", bad, W,
-                  all[K * bad + 3] / 1073741824.0, (unsigned long long)ctx->pk_n, all[K * bad + 4] / 1073741824.0,
+                  all[K * bad + 3] / 1073741824.0, (unsigned long long)ctx->key.n, all[K * bad + 4] / 1073741824.0,
                   (unsigned long long)share);
         throw Error(PNP_E_NOMEM);
     }
@@ -641,17 +639,6 @@ uint64_t *pnp_ctx::buf(const std::string &name, size_t elems_fr) {
 }
 
 using namespace pnp;
-
-#define PNP_TRY(...)                                   \
-    try {                                              \
-        __VA_ARGS__;                                   \
-        return PNP_OK;                                 \
-    } catch (const Error &e) {                         \
-        return e.code;                                 \
-    } catch (const std::exception &e) {                \
-        set_error("exception: %s", e.what());          \
-        return PNP_E_DEVICE;                           \
-    }
 
 extern "C" {
 
@@ -873,7 +860,7 @@ int pnp_hbm_usage(pnp_ctx *ctx, uint64_t out[6]) {
         out[0] = g_dev_live.load();
         out[1] = g_dev_peak.exchange(out[0]);  // the peak since the previous call
         pnp::HbmPlan p;
-        if (ctx && ctx->pk_loaded) p = pnp::hbm_plan(ctx, ctx->pk_n);
+        if (ctx && ctx->key.loaded) p = pnp::hbm_plan(ctx, ctx->key.n);
         out[2] = p.mandatory;
         out[3] = p.lag;
         out[4] = p.groups;
@@ -981,505 +968,6 @@ int pnp_synth_coset_consts(pnp_ctx *ctx, uint64_t *d_vh, uint64_t *d_x, uint32_t
     PNP_TRY(k_coset_consts(d_vh, d_x, lg_n, ctx->stream));
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------- keys + prove
-namespace {
-
-enum FieldKind { kSkip, kEvals8, kCoeffs, kSelEvals8, kSelCoeffs, kTable };
-
-// ProverKeyC field order (lib.rs:157-223) -> how gen_proof uses it.  The
-// q_m, custom-gate and q_lookup selectors (kSel*) are read only when their 8n
-// evaluations are non-zero: for the zero polynomial the Rust prover key holds
-// EMPTY coefficient Vecs (prover.rs:765-808 passes their dangling pointers),
-// so those coefficients are never touched.
-const FieldKind kPkKinds[44] = {
-    kSelCoeffs, kSelEvals8,                           // q_m
-    kCoeffs, kEvals8, kCoeffs, kEvals8, kCoeffs, kEvals8, kCoeffs, kEvals8,  // q_l q_r q_o q_4
-    kCoeffs, kEvals8, kCoeffs, kEvals8, kCoeffs, kEvals8, kCoeffs, kEvals8,  // q_c q_hl q_hr q_h4
-    kCoeffs, kEvals8,                                 // q_arith
-    kSelCoeffs, kSelEvals8, kSelCoeffs, kSelEvals8,   // range, logic selectors
-    kSelCoeffs, kSelEvals8, kSelCoeffs, kSelEvals8,   // fixed / variable group add selectors
-    kSelCoeffs, kSelEvals8,                           // q_lookup
-    kTable, kTable, kTable, kTable,                   // table1..4 (n each, MultiSet::pad)
-    kCoeffs, kEvals8, kCoeffs, kEvals8, kCoeffs, kEvals8, kCoeffs, kEvals8,  // sigmas
-    kEvals8, kEvals8};                                // linear_evaluations, v_h_coset_8n
-// selector fields (coefficients index; evaluations follow): q_m, range,
-// logic, fixed group add, variable group add, q_lookup
-const int kSelField[6] = {0, 20, 22, 24, 26, 28};
-
-bool host_all_zero(const uint64_t *p, uint64_t words) {
-    uint64_t acc = 0;
-    for (uint64_t i = 0; i < words; i++) acc |= p[i];
-    return acc == 0;
-}
-
-
-// ---- steps shared by the two prover-key loads (pnp_load_prover_key: the
-// caller's 8n arrays re-laid into blocks; pnp_load_prover_key_coeffs: the
-// blocks derived from the coefficients) ----
-
-// The quotient's 8n arrays are kept in block layout (point 8j + m -> block m,
-// index j), only the blocks this rank owns: all 8 on one GPU; 8/world when the
-// round-4 pipeline is distributed (pnp_set_exchange_a2a)
-void pk_block_range(pnp_ctx *ctx) {
-    const int world = ctx->msm.world;
-    const bool split = world > 1 && 8 % world == 0 && ctx->msm.alltoall;
-    ctx->pk_nb = split ? 8 / world : 8;
-    ctx->pk_mb0 = split ? ctx->msm.rank * ctx->pk_nb : 0;
-}
-// k_quotient29's keys (protocol.h): no custom gate, no lookup selector or
-// table, the standard coset (the zero flags and pk_std_coset are set)
-bool pk_q29_class(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D) {
-    static const bool q29_on = [] {
-        const char *e = getenv("PNP_QUOT29");
-        return !e || atoi(e) != 0;
-    }();
-    bool q29 = q29_on && ctx->pk_std_coset && ctx->pk_qlookup_zero && !ctx->pk_custom_nz[0] &&
-               !ctx->pk_custom_nz[1] && !ctx->pk_custom_nz[2] && !ctx->pk_custom_nz[3];
-    const uint64_t *tabs[4] = {dev.table1, dev.table2, dev.table3, dev.table4};
-    for (int k = 0; k < 4 && q29; k++)
-        q29 = !tabs[k] || !pnp::k_any_nonzero(tabs[k], 4 * D, ctx->scratch_b, ctx->stream);
-    return q29;
-}
-// the block arrays a q29 key keeps in the 2^261 form (pk_blk29)
-bool pk_name_in29(const char *name) {
-    static const char *const names29[] = {"q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_hl", "q_hr",
-                                          "q_h4", "q_arith", "sig0", "sig1", "sig2", "sig3", "lin"};
-    for (const char *nm : names29)
-        if (strcmp(nm, name) == 0) return true;
-    return false;
-}
-// the sigma n-domain evaluations (gen_proof.cuh:159-165 recomputes
-// NTT.forward(sigma_coeffs) every proof)
-void pk_sigma_domain(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D, uint32_t lg) {
-    const uint64_t *sigc[4] = {dev.left_sigma_coeffs, dev.right_sigma_coeffs, dev.out_sigma_coeffs,
-                               dev.fourth_sigma_coeffs};
-    for (int j = 0; j < 4; j++) {
-        if (ctx->pk_sigma_n[j].bytes < 32 * D) ctx->pk_sigma_n[j].alloc(32 * D);
-        PNP_HIP(hipMemcpyAsync(ctx->pk_sigma_n[j].p, sigc[j], 32 * D, hipMemcpyDeviceToDevice, ctx->stream));
-        pnp::ntt_run(ctx->ntt, ctx->pk_sigma_n[j].u64(), lg, false, false, ctx->stream);
-    }
-}
-// drop the blocks of an earlier key this one does not have
-void pk_prune_blocks(std::map<std::string, pnp::DevBuf> &m, const std::vector<std::string> &u) {
-    for (auto it = m.begin(); it != m.end();)
-        it = std::find(u.begin(), u.end(), it->first) == u.end() ? m.erase(it) : std::next(it);
-}
-// the key is resident: what every load leaves behind
-void pk_load_done(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D) {
-    ctx->pk_blk_rank = ctx->msm.rank;
-    ctx->pk_blk_world = ctx->msm.world;
-    ctx->pk_pinv.release();
-    ctx->pk_pinv_pos = ~0ULL;
-    PNP_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->pk_dev = dev;
-    ctx->pk_n = D;
-    ctx->pk_loaded = true;
-    ctx->hbm_checked = false;  // the budget is checked by the next proof (pnp::hbm_budget)
-}
-
-// The resident key from its coefficient arrays in HBM (`dev`: the *_coeffs and
-// table fields set, NULL = absent), shared by pnp_load_prover_key_coeffs and
-// pnp_preprocess: drops all-zero optional selectors, derives every block
-// array by the per-proof LDE and the coset constants from closed forms.
-void pk_derive_from_coeffs(pnp_ctx *ctx, ProverKeyC &dev, uint64_t D) {
-    uint64_t **dst = reinterpret_cast<uint64_t **>(&dev);
-    // an all-zero optional selector is the zero polynomial too
-    for (int k = 0; k < 6; k++) {
-        const int f = kSelField[k];
-        if (dst[f] && !pnp::k_any_nonzero(dst[f], 4 * D, ctx->scratch_b, ctx->stream)) {
-            dst[f] = nullptr;
-            ctx->pk_owned[f].release();
-        }
-    }
-    ctx->pk_qm_zero = dev.q_m_coeffs == nullptr;
-    ctx->pk_qlookup_zero = dev.q_lookup_coeffs == nullptr;
-    ctx->pk_custom_nz[0] = dev.range_selector_coeffs != nullptr;
-    ctx->pk_custom_nz[1] = dev.logic_selector_coeffs != nullptr;
-    ctx->pk_custom_nz[2] = dev.fixed_group_add_selector_coeffs != nullptr;
-    ctx->pk_custom_nz[3] = dev.variable_group_add_selector_coeffs != nullptr;
-    uint32_t lg = 0;
-    while ((1ULL << lg) < D) lg++;
-    pk_sigma_domain(ctx, dev, D, lg);
-    ctx->pk_std_coset = true;  // a derived key has the standard coset by construction
-    pk_block_range(ctx);
-    const bool q29 = pk_q29_class(ctx, dev, D);
-    // every block array from its n coefficients, on the context's stream
-    // (the tables first: lde_blocks would build them lazily one by one)
-    pnp::ntt_warm(ctx->ntt, lg, ctx->stream);
-    std::vector<std::string> used, used29;
-    const uint64_t blk_elems = (uint64_t)ctx->pk_nb * D;
-    auto slot = [&](const char *name, bool form29) -> uint64_t * {
-        auto &b = (form29 ? ctx->pk_blk29 : ctx->pk_blk)[name];
-        if (b.bytes != 32 * blk_elems) b.alloc(32 * blk_elems);
-        (form29 ? used29 : used).push_back(name);
-        return b.u64();
-    };
-    auto blk = [&](const char *name, const uint64_t *coeffs) {
-        const bool form29 = q29 && pk_name_in29(name);
-        pnp::lde_blocks(ctx->ntt, coeffs, slot(name, form29), lg, ctx->pk_mb0, ctx->pk_nb, ctx->stream, form29);
-    };
-    if (!ctx->pk_qm_zero) blk("q_m", dev.q_m_coeffs);
-    if (!ctx->pk_qlookup_zero) blk("q_lookup", dev.q_lookup_coeffs);
-    if (ctx->pk_custom_nz[0]) blk("range", dev.range_selector_coeffs);
-    if (ctx->pk_custom_nz[1]) blk("logic", dev.logic_selector_coeffs);
-    if (ctx->pk_custom_nz[2]) blk("fixed_add", dev.fixed_group_add_selector_coeffs);
-    if (ctx->pk_custom_nz[3]) blk("var_add", dev.variable_group_add_selector_coeffs);
-    blk("q_l", dev.q_l_coeffs);
-    blk("q_r", dev.q_r_coeffs);
-    blk("q_o", dev.q_o_coeffs);
-    blk("q_4", dev.q_4_coeffs);
-    blk("q_c", dev.q_c_coeffs);
-    blk("q_hl", dev.q_hl_coeffs);
-    blk("q_hr", dev.q_hr_coeffs);
-    blk("q_h4", dev.q_h4_coeffs);
-    blk("q_arith", dev.q_arith_coeffs);
-    blk("sig0", dev.left_sigma_coeffs);
-    blk("sig1", dev.right_sigma_coeffs);
-    blk("sig2", dev.out_sigma_coeffs);
-    blk("sig3", dev.fourth_sigma_coeffs);
-    // the coset constants from their closed forms, straight into the
-    // blocks: lin (2^256 form always: the PI term), its 2^261 form for a
-    // q29 key, v_h^-1, and D (lin - 1), inverted in place into l1v
-    {
-        uint64_t *lin = slot("lin", false), *lin29 = q29 ? slot("lin", true) : nullptr;
-        uint64_t *vh_inv = slot("vh_inv", false), *l1v = slot("l1v", false);
-        pnp::k_coset_blocks(lg, ctx->pk_mb0, ctx->pk_nb, lin, lin29, vh_inv, l1v, ctx->stream);
-        pnp::k_batch_inverse(l1v, blk_elems, ctx->scratch_a, ctx->stream);
-    }
-    pk_prune_blocks(ctx->pk_blk, used);
-    pk_prune_blocks(ctx->pk_blk29, used29);
-    ctx->pk_q29 = q29;
-    // the natural-order scratch of an earlier full load is not needed again
-    PNP_HIP(hipStreamSynchronize(ctx->stream));
-    for (auto &b : ctx->pk_tmp) b.release();
-    pk_load_done(ctx, dev, D);
-}
-
-}  // namespace
-
-extern "C" {
-
-int pnp_load_prover_key(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int device_ptrs) {
-    if (!ctx || !pk || D == 0 || (D & (D - 1)) || D > (1ULL << 25)) return PNP_E_ARG;
-    PNP_TRY({
-        tables_wait(ctx);  // a background build reads the key being replaced: let it finish
-        PNP_HIP(hipSetDevice(ctx->device));
-        ctx->pk_loaded = false;
-        ctx->wire_map_drop();  // (the map of the key being replaced)
-        ctx->pk_gen++;  // derived groups (wires.hip) re-check sigma
-        // device copies are kept across loads and reused when a field's size is
-        // unchanged (the v1 symbol reloads every call: no hipMalloc / hipFree of
-        // ~20 GiB per call)
-        ctx->pk_owned.resize(44);
-        ProverKeyC dev{};
-        uint64_t *const *src = reinterpret_cast<uint64_t *const *>(pk);
-        uint64_t **dst = reinterpret_cast<uint64_t **>(&dev);
-        // non-zero selectors first: they decide which coefficient Vecs exist
-        bool sel_nz[44] = {};
-        for (int k = 0; k < 6; k++) {
-            const int f = kSelField[k] + 1;
-            if (!src[f]) {
-                set_error("prover key field %d is null", f);
-                throw Error(PNP_E_ARG);
-            }
-            const uint64_t words = 4 * 8 * D;
-            const bool nz = device_ptrs ? pnp::k_any_nonzero(src[f], words, ctx->scratch_b, ctx->stream)
-                                        : !host_all_zero(src[f], words);
-            sel_nz[f] = sel_nz[f - 1] = nz;
-        }
-        std::vector<H2D> up;  // host fields, uploaded together (h2d_batch)
-        for (int f = 0; f < 44; f++) {
-            FieldKind k = kPkKinds[f];
-            dst[f] = nullptr;
-            if (k == kSkip || ((k == kSelEvals8 || k == kSelCoeffs) && !sel_nz[f])) {
-                ctx->pk_owned[f].release();
-                continue;
-            }
-            uint64_t elems = (k == kEvals8 || k == kSelEvals8) ? 8 * D : D;
-            if (!src[f]) {
-                set_error("prover key field %d is null", f);
-                throw Error(PNP_E_ARG);
-            }
-            if (device_ptrs) {
-                ctx->pk_owned[f].release();
-                dst[f] = src[f];
-            } else {
-                auto &o = ctx->pk_owned[f];
-                if (o.bytes != elems * 32) o.alloc(elems * 32);
-                up.push_back({o.p, src[f], elems * 32});
-                dst[f] = o.u64();
-            }
-        }
-        h2d_batch(ctx, up);
-        // key-derived constants, computed once per key instead of per proof:
-        // zero-selector flags (the quotient kernel skips known-zero selectors)
-        // and the sigma n-domain evaluations (gen_proof.cuh:159-165 recomputes
-        // NTT.forward(sigma_coeffs) every proof)
-        ctx->pk_qm_zero = dev.q_m_evals == nullptr;
-        ctx->pk_qlookup_zero = dev.q_lookup_evals == nullptr;
-        ctx->pk_custom_nz[0] = dev.range_selector_evals != nullptr;
-        ctx->pk_custom_nz[1] = dev.logic_selector_evals != nullptr;
-        ctx->pk_custom_nz[2] = dev.fixed_group_add_selector_evals != nullptr;
-        ctx->pk_custom_nz[3] = dev.variable_group_add_selector_evals != nullptr;
-        uint32_t lg = 0;
-        while ((1ULL << lg) < D) lg++;
-        pk_sigma_domain(ctx, dev, D, lg);
-        // coset constants: v_h^-1 (the reference divides by v_h every proof,
-        // quotient.cu:369-370); when the key's coset arrays are the standard
-        // ones (x_i = 7 w_8n^i, v_h = x^n - 1, as every key built by the
-        // reference's preprocessing), the L1 and PI coset evaluations have the
-        // closed forms of protocol.h and need no LDE per proof
-        const uint64_t N8 = 8 * D;
-        auto tmp = [&](int k) -> pnp::DevBuf & {  // per-load scratch, kept for the next load
-            if (ctx->pk_tmp[k].bytes != 32 * N8) ctx->pk_tmp[k].alloc(32 * N8);
-            return ctx->pk_tmp[k];
-        };
-        pnp::DevBuf &vh_inv = tmp(0), &l1v = tmp(1);
-        PNP_HIP(hipMemcpyAsync(vh_inv.p, dev.v_h_coset_8n, 32 * N8, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        pnp::k_batch_inverse(vh_inv.u64(), N8, ctx->scratch_a, ctx->stream);
-        {
-            pnp::DevBuf &vh = tmp(2), &x = tmp(3);
-            pnp::k_coset_consts(vh.u64(), x.u64(), lg, ctx->stream);
-            ctx->pk_std_coset =
-                !pnp::k_any_diff(vh.u64(), dev.v_h_coset_8n, 4 * N8, ctx->scratch_b, ctx->stream) &&
-                !pnp::k_any_diff(x.u64(), dev.linear_evaluations, 4 * N8, ctx->scratch_b, ctx->stream);
-            if (ctx->pk_std_coset) {
-                pnp::k_affine(l1v.u64(), x.u64(), Fr::one(), pnp::neg(Fr::one()), N8, ctx->stream);
-                pnp::k_batch_inverse(l1v.u64(), N8, ctx->scratch_a, ctx->stream);
-                Fr nf = Fr::zero();
-                nf.v[0] = (uint32_t)D;
-                nf.v[1] = (uint32_t)(D >> 32);
-                pnp::k_affine(l1v.u64(), l1v.u64(), pnp::inverse(pnp::to_mont(nf)), Fr::zero(), N8,
-                              ctx->stream);
-            }
-            PNP_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        // the blocks this rank owns (pk_block_range)
-        pk_block_range(ctx);
-        // k_quotient29's keys (pk_q29_class): their selector / sigma / lin
-        // blocks are kept in the 2^261 form (pk_blk29) and, but lin (the PI
-        // term), not in the 2^256 form at all
-        const bool q29 = pk_q29_class(ctx, dev, D);
-        std::vector<std::string> used, used29;
-        const uint64_t blk_elems = (uint64_t)ctx->pk_nb * D;
-        auto put = [&](std::map<std::string, pnp::DevBuf> &m, std::vector<std::string> &u, const char *name,
-                       const uint64_t *src, bool form29) {
-            auto &b = m[name];
-            if (b.bytes != 32 * blk_elems) b.alloc(32 * blk_elems);
-            pnp::to_blocks(src, b.u64(), lg, ctx->pk_mb0, ctx->pk_nb, ctx->stream);
-            if (form29) pnp::k_to_form29(b.u64(), b.u64(), blk_elems, ctx->stream);  // elementwise, in place
-            u.push_back(name);
-        };
-        auto blk = [&](const char *name, const uint64_t *src) {
-            const bool in29 = pk_name_in29(name);
-            if (q29 && in29) put(ctx->pk_blk29, used29, name, src, true);
-            if (!(q29 && in29) || strcmp(name, "lin") == 0) put(ctx->pk_blk, used, name, src, false);
-        };
-        if (!ctx->pk_qm_zero) blk("q_m", dev.q_m_evals);
-        if (!ctx->pk_qlookup_zero) blk("q_lookup", dev.q_lookup_evals);
-        if (ctx->pk_custom_nz[0]) blk("range", dev.range_selector_evals);
-        if (ctx->pk_custom_nz[1]) blk("logic", dev.logic_selector_evals);
-        if (ctx->pk_custom_nz[2]) blk("fixed_add", dev.fixed_group_add_selector_evals);
-        if (ctx->pk_custom_nz[3]) blk("var_add", dev.variable_group_add_selector_evals);
-        blk("q_l", dev.q_l_evals);
-        blk("q_r", dev.q_r_evals);
-        blk("q_o", dev.q_o_evals);
-        blk("q_4", dev.q_4_evals);
-        blk("q_c", dev.q_c_evals);
-        blk("q_hl", dev.q_hl_evals);
-        blk("q_hr", dev.q_hr_evals);
-        blk("q_h4", dev.q_h4_evals);
-        blk("q_arith", dev.q_arith_evals);
-        blk("sig0", dev.left_sigma_evals);
-        blk("sig1", dev.right_sigma_evals);
-        blk("sig2", dev.out_sigma_evals);
-        blk("sig3", dev.fourth_sigma_evals);
-        blk("lin", dev.linear_evaluations);
-        blk("vh_inv", vh_inv.u64());
-        if (ctx->pk_std_coset) blk("l1v", l1v.u64());
-        // blocks of an earlier key this one does not have
-        pk_prune_blocks(ctx->pk_blk, used);
-        pk_prune_blocks(ctx->pk_blk29, used29);
-        ctx->pk_q29 = q29;
-        // the coset-constant scratch (4 x 8n Fr) is kept only for callers that
-        // load keys from host memory again and again (the v1 symbol); a
-        // device-resident key is loaded once (and ranks sharing a GPU need the
-        // HBM)
-        if (device_ptrs) {
-            PNP_HIP(hipStreamSynchronize(ctx->stream));
-            for (auto &b : ctx->pk_tmp) b.release();
-        }
-        pk_load_done(ctx, dev, D);
-    });
-}
-
-// The same resident key from the coefficient arrays alone: every 8n array of
-// a key built by the reference's preprocessing is coset_fft of a coefficient
-// array the struct also carries (preprocess.rs:174-255) or a function of n
-// (linear_evaluations, v_h_coset_8n: preprocess.rs:257-264), so the blocks
-// pnp_load_prover_key copies out of the caller's arrays are derived here, by
-// the per-proof LDE (lde_blocks) and from closed forms (k_coset_blocks), and
-// nothing 8n-sized crosses PCIe or stays resident beside the blocks.
-int pnp_load_prover_key_coeffs(pnp_ctx *ctx, const ProverKeyC *pk, uint64_t D, int device_ptrs) {
-    if (!ctx || !pk || D == 0 || (D & (D - 1)) || D > (1ULL << 25)) return PNP_E_ARG;
-    uint64_t *const *src = reinterpret_cast<uint64_t *const *>(pk);
-    // the required fields are checked before anything is touched: a refused
-    // call leaves the resident key as it was
-    for (int f = 0; f < 44; f++)
-        if ((kPkKinds[f] == kCoeffs || kPkKinds[f] == kTable) && !src[f]) {
-            set_error("prover key field %d is null", f);
-            return PNP_E_ARG;
-        }
-    PNP_TRY({
-        tables_wait(ctx);  // a background build reads the key being replaced: let it finish
-        PNP_HIP(hipSetDevice(ctx->device));
-        ctx->pk_loaded = false;
-        ctx->wire_map_drop();  // (the map of the key being replaced)
-        ctx->pk_gen++;
-        ctx->pk_owned.resize(44);
-        ProverKeyC dev{};
-        uint64_t **dst = reinterpret_cast<uint64_t **>(&dev);
-        std::vector<H2D> up;
-        for (int f = 0; f < 44; f++) {
-            const FieldKind k = kPkKinds[f];
-            dst[f] = nullptr;
-            // never read: the evaluations; an optional selector without
-            // coefficients is the zero polynomial
-            if (k == kSkip || k == kEvals8 || k == kSelEvals8 || (k == kSelCoeffs && !src[f])) {
-                ctx->pk_owned[f].release();
-                continue;
-            }
-            if (device_ptrs) {
-                ctx->pk_owned[f].release();
-                dst[f] = src[f];
-            } else {
-                auto &o = ctx->pk_owned[f];
-                if (o.bytes != D * 32) o.alloc(D * 32);
-                up.push_back({o.p, src[f], D * 32});
-                dst[f] = o.u64();
-            }
-        }
-        h2d_batch(ctx, up);
-        pk_derive_from_coeffs(ctx, dev, D);
-    });
-}
-
-}  // extern "C"
-
-namespace {
-
-// pnp_circuit_desc.sel[k] -> its coefficient field of ProverKeyC, and whether
-// an absent column leaves the field NULL (kSelField) or is a column of zeros
-const int kDescSelField[15] = {0, 2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28};
-const bool kDescSelOptional[15] = {true, false, false, false, false, false, false, false,
-                                   false, false, true, true, true, true, true};
-const int kTableField[4] = {30, 31, 32, 33};
-const int kSigmaField[4] = {34, 36, 38, 40};
-// pnp_verifier_key.polys[k] -> the ProverKeyC field holding its polynomial
-// (the tables are kept as padded columns: committed from a transformed copy)
-const int kVkField[PNP_VK_POLYS] = {0,  2,  4,  6,  8,  10, 12, 14, 16, 18, 20, 22,
-                                    24, 26, 34, 36, 38, 40, 28, 30, 31, 32, 33};
-
-bool bad_variable(uint64_t slot, uint64_t n_vars) {
-    if (slot == ~0ULL) return false;
-    set_error("variable id >= n_vars (%llu) in wire %d of row %llu", (unsigned long long)n_vars, (int)(slot & 3),
-              (unsigned long long)(slot >> 2));
-    return true;
-}
-
-// the caller's four id columns (host or HBM) as one array the library owns:
-// column j at u32 offset j * ng
-void wire_map_copy(pnp_ctx *ctx, const uint32_t *const var[4], uint64_t ng, int device_ptrs, pnp::DevBuf &out) {
-    out.alloc(16 * ng);
-    std::vector<H2D> up;
-    for (int j = 0; j < 4; j++) {
-        uint32_t *d = static_cast<uint32_t *>(out.p) + j * ng;
-        if (device_ptrs) PNP_HIP(hipMemcpyAsync(d, var[j], 4 * ng, hipMemcpyDeviceToDevice, ctx->stream));
-        else up.push_back({d, var[j], 4 * ng});
-    }
-    if (!up.empty()) h2d_batch(ctx, up);
-}
-
-// `var` (wire_map_copy) becomes the resident wire map of the resident key, and
-// the q_lookup row values are derived from the key's coefficients (a forward
-// transform; nothing is kept for the zero polynomial)
-void wire_map_adopt(pnp_ctx *ctx, pnp::DevBuf &var, uint64_t ng, uint64_t n_vars) {
-    ctx->wire_map_drop();
-    const uint64_t D = ctx->pk_n;
-    if (ctx->pk_dev.q_lookup_coeffs) {
-        uint32_t lg = 0;
-        while ((1ULL << lg) < D) lg++;
-        ctx->wm_qlk.alloc(32 * D);
-        PNP_HIP(hipMemcpyAsync(ctx->wm_qlk.p, ctx->pk_dev.q_lookup_coeffs, 32 * D, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        pnp::ntt_run(ctx->ntt, ctx->wm_qlk.u64(), lg, false, false, ctx->stream);  // (as pk_sigma_domain)
-        PNP_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->wm_var = std::move(var);
-    ctx->wm_gates = ng;
-    ctx->wm_vars = n_vars;
-    ctx->wm_loaded = true;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pnp_load_wire_map(pnp_ctx *ctx, const uint32_t *const var[4], uint64_t n_gates, uint64_t n_vars,
-                      int device_ptrs) {
-    if (!ctx || !var || !var[0] || !var[1] || !var[2] || !var[3] || n_gates == 0) return PNP_E_ARG;
-    if (!ctx->pk_loaded) {
-        set_error("load wire map: prover key not loaded");
-        return PNP_E_NOKEY;
-    }
-    if (ctx->msm.world > 1) {
-        set_error("load wire map: the context is sharded over %d ranks (multi-rank wire maps are not supported)",
-                  ctx->msm.world);
-        return PNP_E_ARG;
-    }
-    const uint64_t D = ctx->pk_n;
-    if (n_gates > D) {
-        set_error("load wire map: %llu gates, the resident key's domain has %llu rows", (unsigned long long)n_gates,
-                  (unsigned long long)D);
-        return PNP_E_ARG;
-    }
-    PNP_TRY({
-        tables_wait(ctx);  // (the NTT tables are shared with a background build)
-        PNP_HIP(hipSetDevice(ctx->device));
-        ctx->wire_map_drop();  // a refused map leaves none resident
-        uint32_t lg = 0;
-        while ((1ULL << lg) < D) lg++;
-        pnp::DevBuf ids;
-        wire_map_copy(ctx, var, n_gates, device_ptrs, ids);
-        {
-            // the sigmas of this map must be the resident key's (the forward
-            // transforms of its sigma coefficients, kept since the key load)
-            pnp::DevBuf sig[4], next(16 * D), sort, first;
-            const uint32_t *base = static_cast<const uint32_t *>(ids.p);
-            const uint32_t *dvar[4] = {base, base + n_gates, base + 2 * n_gates, base + 3 * n_gates};
-            uint64_t *dsig[4];
-            const uint64_t *csig[4], *ksig[4];
-            for (int j = 0; j < 4; j++) {
-                sig[j].alloc(32 * D);
-                csig[j] = dsig[j] = sig[j].u64();
-                ksig[j] = ctx->pk_sigma_n[j].u64();
-            }
-            const uint64_t bad = pnp::wire_sigma(ctx->ntt, dvar, n_gates, n_vars, lg, static_cast<uint32_t *>(next.p),
-                                                 dsig, sort, ctx->stream);
-            if (bad_variable(bad, n_vars)) throw Error(PNP_E_ARG);
-            const uint64_t diff = pnp::k_first_diff4(csig, ksig, lg, first, ctx->stream);
-            if (diff != ~0ULL) {
-                set_error("load wire map: the map's sigma differs from the resident key's in wire %d of row %llu",
-                          (int)(diff & 3), (unsigned long long)(diff >> 2));
-                throw Error(PNP_E_ARG);
-            }
-        }  // (the scratch is released here)
-        wire_map_adopt(ctx, ids, n_gates, n_vars);
-    });
-}
 
 int pnp_gather_witness(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates, const uint64_t *d_values,
                        uint64_t n_vars, uint32_t lg_n, uint64_t *const d_w[4]) {
@@ -1494,190 +982,9 @@ int pnp_gather_witness(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_
     });
 }
 
-int pnp_wire_sigma(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, uint32_t lg_n,
-                   uint32_t *d_next, uint64_t *const d_sigma[4]) {
-    if (!ctx || !d_var || !d_var[0] || !d_var[1] || !d_var[2] || !d_var[3] || n_gates == 0 || lg_n > 25 ||
-        n_gates > (1ULL << lg_n))
-        return PNP_E_ARG;
-    PNP_TRY({
-        tables_wait(ctx);  // (the NTT tables are shared with a background build)
-        PNP_HIP(hipSetDevice(ctx->device));
-        pnp::DevBuf next, sort;
-        if (!d_next) {
-            next.alloc(16ULL << lg_n);
-            d_next = static_cast<uint32_t *>(next.p);
-        }
-        const uint64_t bad =
-            pnp::wire_sigma(ctx->ntt, d_var, n_gates, n_vars, lg_n, d_next, d_sigma, sort, ctx->stream);
-        if (bad_variable(bad, n_vars)) throw Error(PNP_E_ARG);
-    });
-}
-
-// Circuit::compile on the device: the padded columns and the sigmas of the
-// wire map inverse-transformed into the arrays pnp_load_prover_key_coeffs
-// would have been handed, then its derivation (pk_derive_from_coeffs), then
-// the verifier key's commitments.
-int pnp_preprocess(pnp_ctx *ctx, const pnp_circuit_desc *c, int device_ptrs, pnp_verifier_key *vk) {
-    if (!ctx || !c) return PNP_E_ARG;
-    const uint64_t ng = c->n_gates, tl = c->lookup_len;
-    if (ng == 0 || ng > (1ULL << 25) || tl > (1ULL << 25)) {
-        set_error("preprocess: %llu gates, %llu table rows (1 <= gates, domain <= 2^25)", (unsigned long long)ng,
-                  (unsigned long long)tl);
-        return PNP_E_ARG;
-    }
-    uint64_t D = 1;
-    uint32_t lg = 0;
-    while (D < std::max(ng, tl)) D <<= 1, lg++;
-    // every refusal comes before the resident key is touched
-    for (int j = 0; j < 4; j++) {
-        if (!c->var[j]) {
-            set_error("preprocess: var[%d] is null", j);
-            return PNP_E_ARG;
-        }
-        if (tl && !c->table[j]) {
-            set_error("preprocess: table[%d] is null with %llu table rows", j, (unsigned long long)tl);
-            return PNP_E_ARG;
-        }
-    }
-    if (ctx->msm.world > 1) {
-        set_error("preprocess: the context is sharded over %d ranks (multi-rank preprocessing is not supported)",
-                  ctx->msm.world);
-        return PNP_E_ARG;
-    }
-    if (vk && (!ctx->ck_loaded || ctx->ck_points < D)) {
-        set_error("preprocess: the verifier key needs a commit key of %llu points (%llu loaded)",
-                  (unsigned long long)D, (unsigned long long)(ctx->ck_loaded ? ctx->ck_points : 0));
-        return PNP_E_NOKEY;
-    }
-    PNP_TRY({
-        tables_wait(ctx);  // a background build reads the key being replaced: let it finish
-        PNP_HIP(hipSetDevice(ctx->device));
-        using clk = std::chrono::steady_clock;
-        double t_up = 0, t_perm = 0, t_intt = 0, t_derive = 0, t_vk = 0, h2d_bytes = 0;
-        auto t0 = clk::now();
-        auto lap = [&](double &acc) {  // (every stage ends synchronised)
-            PNP_HIP(hipStreamSynchronize(ctx->stream));
-            const auto t1 = clk::now();
-            acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
-            t0 = t1;
-        };
-        // the permutation first, into scratch: a bad id is an argument error
-        // (the ids are copied whichever side they come from: the copy becomes
-        // the resident wire map of the new key)
-        pnp::DevBuf sig[4], vars;
-        {
-            pnp::DevBuf next(16 * D), sort;
-            wire_map_copy(ctx, c->var, ng, device_ptrs, vars);
-            if (!device_ptrs) h2d_bytes += 16.0 * ng;
-            const uint32_t *vbase = static_cast<const uint32_t *>(vars.p);
-            const uint32_t *dvar[4] = {vbase, vbase + ng, vbase + 2 * ng, vbase + 3 * ng};
-            lap(t_up);
-            uint64_t *dsig[4];
-            for (int j = 0; j < 4; j++) {
-                sig[j].alloc(32 * D);
-                dsig[j] = sig[j].u64();
-            }
-            pnp::WireSigmaStats st;
-            const uint64_t bad = pnp::wire_sigma(ctx->ntt, dvar, ng, c->n_vars, lg, static_cast<uint32_t *>(next.p),
-                                                 dsig, sort, ctx->stream, &st);
-            if (bad_variable(bad, c->n_vars)) throw Error(PNP_E_ARG);
-            ctx->stages.clear();
-            ctx->stages.push_back({"pre_permutation_bytes", st.bytes});
-        }  // (the sort scratch and next are released here)
-        lap(t_perm);
-        // ---- the resident key is replaced from here on, and its wire map with it
-        ctx->wire_map_drop();
-        ctx->pk_loaded = false;
-        ctx->pk_gen++;
-        ctx->pk_owned.resize(44);
-        ProverKeyC dev{};
-        uint64_t **dst = reinterpret_cast<uint64_t **>(&dev);
-        for (int f = 0; f < 44; f++)
-            if (kPkKinds[f] != kCoeffs && kPkKinds[f] != kSelCoeffs && kPkKinds[f] != kTable)
-                ctx->pk_owned[f].release();
-        std::vector<H2D> up;
-        auto column = [&](int f, const uint64_t *src, uint64_t len, bool first) {
-            auto &o = ctx->pk_owned[f];
-            if (o.bytes != D * 32) o.alloc(D * 32);
-            dst[f] = o.u64();
-            if (!src || !len) {
-                PNP_HIP(hipMemsetAsync(o.p, 0, D * 32, ctx->stream));
-            } else if (device_ptrs) {
-                pnp::k_pad_col(o.u64(), src, len, D, first, ctx->stream);
-            } else {
-                up.push_back({o.p, src, len * 32});
-                h2d_bytes += 32.0 * len;
-            }
-        };
-        for (int k = 0; k < 15; k++) {
-            const int f = kDescSelField[k];
-            if (!c->sel[k] && kDescSelOptional[k]) ctx->pk_owned[f].release();
-            else column(f, c->sel[k], ng, false);
-        }
-        for (int j = 0; j < 4; j++) column(kTableField[j], tl ? c->table[j] : nullptr, tl, true);
-        if (!device_ptrs) {
-            h2d_batch(ctx, up);
-            for (int k = 0; k < 15; k++)
-                if (c->sel[k]) pnp::k_pad_col(dst[kDescSelField[k]], dst[kDescSelField[k]], ng, D, false, ctx->stream);
-            for (int j = 0; j < 4 && tl; j++)
-                pnp::k_pad_col(dst[kTableField[j]], dst[kTableField[j]], tl, D, true, ctx->stream);
-        }
-        for (int j = 0; j < 4; j++) {
-            ctx->pk_owned[kSigmaField[j]] = std::move(sig[j]);
-            dst[kSigmaField[j]] = ctx->pk_owned[kSigmaField[j]].u64();
-        }
-        lap(t_up);
-        // row values -> coefficients (the tables stay columns: ProverKeyC.table1..4)
-        for (int f = 0; f < 44; f++)
-            if (dst[f] && kPkKinds[f] != kTable) pnp::ntt_run(ctx->ntt, dst[f], lg, true, false, ctx->stream);
-        lap(t_intt);
-        pk_derive_from_coeffs(ctx, dev, D);
-        wire_map_adopt(ctx, vars, ng, c->n_vars);
-        lap(t_derive);
-        if (vk) {
-            vk->n = D;
-            PNP_HIP(hipMemcpyAsync(vk->g, ctx->ck_dev, 96, hipMemcpyDeviceToHost, ctx->stream));
-            const uint64_t *const *res = reinterpret_cast<const uint64_t *const *>(&ctx->pk_dev);
-            pnp::DevBuf tabc[4];
-            std::vector<const uint64_t *> sc;
-            std::vector<CommitmentC *> oc;
-            uint64_t one[6];
-            to_u64_limbs(Fq::one(), one);
-            for (int k = 0; k < PNP_VK_POLYS; k++) {
-                const int f = kVkField[k];
-                const uint64_t *p = res[f];
-                // (a mandatory selector or a table may be all zero too)
-                if (p && !pnp::k_any_nonzero(p, 4 * D, ctx->scratch_b, ctx->stream)) p = nullptr;
-                if (p && kPkKinds[f] == kTable) {
-                    pnp::DevBuf &t = tabc[f - kTableField[0]];
-                    t.alloc(32 * D);
-                    PNP_HIP(hipMemcpyAsync(t.p, p, 32 * D, hipMemcpyDeviceToDevice, ctx->stream));
-                    pnp::ntt_run(ctx->ntt, t.u64(), lg, true, false, ctx->stream);
-                    p = t.u64();
-                }
-                if (!p) {  // the zero polynomial
-                    memset(vk->polys[k].x, 0, 48);
-                    memcpy(vk->polys[k].y, one, 48);
-                    continue;
-                }
-                sc.push_back(p);
-                oc.push_back(&vk->polys[k]);
-            }
-            for (size_t b = 0; b < sc.size(); b += 8)
-                pnp::commit_affine_batch(ctx, sc.data() + b, (int)std::min<size_t>(8, sc.size() - b), D, oc.data() + b);
-            lap(t_vk);
-        }
-        ctx->stages.push_back({"pre_upload", t_up});
-        ctx->stages.push_back({"pre_permutation", t_perm});
-        ctx->stages.push_back({"pre_intt", t_intt});
-        ctx->stages.push_back({"pre_derive", t_derive});
-        ctx->stages.push_back({"pre_vk", t_vk});
-        ctx->stages.push_back({"pre_h2d_bytes", h2d_bytes});
-    });
-}
-
 }  // extern "C"
 
+// ---------------------------------------------------------------- keys + prove
 namespace {
 
 // make `up` (n_points packed affine points in HBM) the resident SRS.  The
@@ -1876,9 +1183,11 @@ namespace {
 // which this backend returns the ZK-Garage prover's proof while the reference
 // GPU path would return a different one.
 bool key_tables_zero(pnp_ctx *ctx) {
-    const uint64_t *t[4] = {ctx->pk_dev.table1, ctx->pk_dev.table2, ctx->pk_dev.table3, ctx->pk_dev.table4};
-    for (const uint64_t *p : t)
-        if (p && pnp::k_any_nonzero(p, 4 * ctx->pk_n, ctx->scratch_b, ctx->stream)) return false;
+    const uint64_t *const *f = reinterpret_cast<const uint64_t *const *>(&ctx->key.dev);
+    for (const KeyRow &r : kKeyTable)
+        if (r.cls == kTable && f[r.coeffs] &&
+            pnp::k_any_nonzero(f[r.coeffs], 4 * ctx->key.n, ctx->scratch_b, ctx->stream))
+            return false;
     return true;
 }
 uint64_t mix64(uint64_t h, uint64_t v) {
@@ -1893,14 +1202,13 @@ uint64_t sample_words(uint64_t h, const uint64_t *p, uint64_t words) {
 uint64_t pk_fingerprint(const ProverKeyC &pk, uint64_t D) {
     uint64_t *const *f = reinterpret_cast<uint64_t *const *>(&pk);
     uint64_t h = mix64(0x1234567ULL, D);
-    for (int i = 0; i < 44; i++) {
+    for (int i = 0; i < kPkFields; i++) {
         h = mix64(h, reinterpret_cast<uintptr_t>(f[i]));
-        FieldKind k = kPkKinds[i];
+        const KeyField fld = key_field(i);
         // selector coefficients may be empty Vecs: pointer only (their
         // evaluations, sampled, decide whether they are read)
-        if (k == kSkip || k == kSelCoeffs || !f[i]) continue;
-        const uint64_t elems = (k == kEvals8 || k == kSelEvals8) ? 8 * D : D;
-        h = sample_words(h, f[i], 4 * elems);
+        if ((fld.row->optional() && !fld.evals) || !f[i]) continue;
+        h = sample_words(h, f[i], 4 * fld.elems(D));
     }
     return h;
 }
@@ -1989,16 +1297,18 @@ std::array<uint64_t, 2> pk_content_hash(const ProverKeyC &pk, uint64_t D, unsign
     uint64_t *const *f = reinterpret_cast<uint64_t *const *>(&pk);
     std::vector<Seg> segs;
     std::vector<int> field;
-    for (int i = 0; i < 44; i++) {
-        const FieldKind k = kPkKinds[i];
-        if (k == kSkip || k == kSelCoeffs || !f[i]) continue;
-        segs.push_back({f[i], 4 * ((k == kEvals8 || k == kSelEvals8) ? 8 * D : D)});
+    for (int i = 0; i < kPkFields; i++) {
+        const KeyField fld = key_field(i);
+        if ((fld.row->optional() && !fld.evals) || !f[i]) continue;
+        segs.push_back({f[i], 4 * fld.elems(D)});
         field.push_back(i);
     }
     std::vector<SegHash> h = hash_segments(segs, cap);
     std::vector<Seg> sel;
-    for (size_t j = 0; j < segs.size(); j++)
-        if (kPkKinds[field[j]] == kSelEvals8 && h[j].nz && f[field[j] - 1]) sel.push_back({f[field[j] - 1], 4 * D});
+    for (size_t j = 0; j < segs.size(); j++) {
+        const KeyRow &r = *key_field(field[j]).row;  // (an optional row is here with its evaluations)
+        if (r.optional() && h[j].nz && f[r.coeffs]) sel.push_back({f[r.coeffs], 4 * D});
+    }
     std::vector<SegHash> hs = hash_segments(sel, cap);
     std::array<uint64_t, 2> r = {mix64(0xABCDEFULL, D), mix64(0xFEDCBAULL, D)};
     for (size_t j = 0; j < h.size(); j++) {
@@ -2039,24 +1349,13 @@ struct V1KeyLoad {
     bool tried = false, derived = false, fell_back = false;
     double ms_scan = 0, ms_derive = 0, ms_fallback = 0;
 };
-// block name of the 8n array in ProverKeyC field f (nullptr: not an 8n array)
-const char *pk_eval_block(int f) {
-    static const char *const names[44] = {
-        nullptr, "q_m", nullptr, "q_l", nullptr, "q_r", nullptr, "q_o", nullptr, "q_4", nullptr, "q_c",
-        nullptr, "q_hl", nullptr, "q_hr", nullptr, "q_h4", nullptr, "q_arith", nullptr, "range",
-        nullptr, "logic", nullptr, "fixed_add", nullptr, "var_add", nullptr, "q_lookup",
-        nullptr, nullptr, nullptr, nullptr, nullptr, "sig0", nullptr, "sig1", nullptr, "sig2",
-        nullptr, "sig3", "lin", "vh_inv"};
-    return names[f];
-}
 // the sampled elements of the caller's 8n arrays against the derived blocks
 // (gathered on the device from the block layout; the blocks another rank owns
 // are skipped); false: some element differs
 bool v1_sampled_check(pnp_ctx *ctx, const ProverKeyC &pk, uint64_t D) {
     uint64_t *const *f = reinterpret_cast<uint64_t *const *>(&pk);
     const uint64_t K = 256, words = 4 * 8 * D;
-    uint32_t lg = 0;
-    while ((1ULL << lg) < D) lg++;
+    const uint32_t lg = log2_exact(D);
     std::vector<uint64_t> idx(K + 1);
     for (uint64_t k = 0; k <= K; k++) idx[k] = ((words - 1) * k / K) / 4;  // element of sampled word k
     const uint32_t cnt = (uint32_t)idx.size();
@@ -2066,12 +1365,12 @@ bool v1_sampled_check(pnp_ctx *ctx, const ProverKeyC &pk, uint64_t D) {
     };
     std::vector<Arr> arrs;
     std::vector<const uint64_t *> blks;
-    for (int i = 0; i < 44; i++) {
-        const char *name = pk_eval_block(i);
-        if (!name) continue;
+    for (int i = 0; i < kPkFields; i++) {  // every 8n array, in field order
+        const KeyField fld = key_field(i);
+        if (!fld.evals) continue;
         if (!f[i]) return false;  // the full load refuses it: let it say so
-        const uint64_t *b = ctx->blk(name), *b29 = ctx->blk29(name);
-        arrs.push_back({i, i == 43 ? 3 : b ? 1 : b29 ? 2 : 0});
+        const uint64_t *b = ctx->key.blk[fld.row->id].u64(), *b29 = ctx->key.blk29[fld.row->id].u64();
+        arrs.push_back({i, fld.row->id == kVhInv ? 3 : b ? 1 : b29 ? 2 : 0});
         blks.push_back(b ? b : b29);
     }
     pnp::DevBuf d_idx(8 * cnt), d_out(32 * (size_t)cnt * arrs.size());
@@ -2079,7 +1378,7 @@ bool v1_sampled_check(pnp_ctx *ctx, const ProverKeyC &pk, uint64_t D) {
     PNP_HIP(hipMemcpyAsync(d_idx.p, idx.data(), 8 * cnt, hipMemcpyHostToDevice, ctx->stream));
     for (size_t a = 0; a < arrs.size(); a++)
         if (blks[a])
-            pnp::k_gather_blocks(blks[a], lg, ctx->pk_mb0, ctx->pk_nb, d_idx.u64(), cnt, d_out.u64() + 4 * cnt * a,
+            pnp::k_gather_blocks(blks[a], lg, ctx->key.mb0, ctx->key.nb, d_idx.u64(), cnt, d_out.u64() + 4 * cnt * a,
                                  ctx->stream);
     PNP_HIP(hipMemcpyAsync(got.data(), d_out.p, 8 * got.size(), hipMemcpyDeviceToHost, ctx->stream));
     PNP_HIP(hipStreamSynchronize(ctx->stream));
@@ -2095,7 +1394,7 @@ bool v1_sampled_check(pnp_ctx *ctx, const ProverKeyC &pk, uint64_t D) {
                 if (memcmp(mine, zero, 32)) return false;
                 continue;
             }
-            if (m < ctx->pk_mb0 || m >= ctx->pk_mb0 + ctx->pk_nb) continue;
+            if (m < ctx->key.mb0 || m >= ctx->key.mb0 + ctx->key.nb) continue;
             uint64_t want[4];
             if (arrs[a].form == 1) {
                 memcpy(want, mine, 32);
@@ -2121,18 +1420,24 @@ int v1_load_prover_key(pnp_ctx *ctx, const ProverKeyC &pk, uint64_t D, V1KeyLoad
     st.tried = true;
     uint64_t *const *f = reinterpret_cast<uint64_t *const *>(&pk);
     bool usable = true;
-    for (int k = 0; k < 6; k++) usable &= f[kSelField[k] + 1] != nullptr;
+    for (const KeyRow &r : kKeyTable)
+        if (r.optional()) usable &= f[r.evals] != nullptr;
     if (usable) {
         // which optional selectors exist: their first D evaluations, scanned on
         // the hash thread pool
         auto t = clk::now();
         std::vector<Seg> segs;
-        for (int k = 0; k < 6; k++) segs.push_back({f[kSelField[k] + 1], 4 * D});
+        std::vector<int> coeffs;
+        for (const KeyRow &r : kKeyTable)
+            if (r.optional()) {
+                segs.push_back({f[r.evals], 4 * D});
+                coeffs.push_back(r.coeffs);
+            }
         const std::vector<SegHash> h = hash_segments(segs, cap);
         ProverKeyC compact = pk;
         uint64_t **c = reinterpret_cast<uint64_t **>(&compact);
-        for (int k = 0; k < 6; k++)
-            if (!h[k].nz) c[kSelField[k]] = nullptr;
+        for (size_t k = 0; k < segs.size(); k++)
+            if (!h[k].nz) c[coeffs[k]] = nullptr;
         st.ms_scan = ms_since(t);
         t = clk::now();
         bool ok = pnp_load_prover_key_coeffs(ctx, &compact, D, 0) == PNP_OK;
@@ -2234,8 +1539,8 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
     // what identifies "the same key": the full-content hash (default), the
     // sampled fingerprint (PNP_V1_REUSE), nothing (PNP_V1_RELOAD: upload always)
     std::array<uint64_t, 2> hp{}, hc{};
-    const bool speculate = !reuse && !reload && have_pk && have_ck && ctx->pk_loaded && ctx->ck_loaded &&
-                           ctx->pk_n == D && ctx->ck_points == D && !env_on("PNP_V1_NO_SPECULATE");
+    const bool speculate = !reuse && !reload && have_pk && have_ck && ctx->key.loaded && ctx->ck_loaded &&
+                           ctx->key.n == D && ctx->ck_points == D && !env_on("PNP_V1_NO_SPECULATE");
     if (speculate) {
         // hash on the other cores (one fewer than the hash would take alone:
         // this thread drives the proof) while the proof runs on the resident keys
@@ -2270,7 +1575,7 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
         hp = {pk_fingerprint(pk, D), D};
         hc = {ck_fingerprint(ck, D), D};
     } else if (!reload) {
-        const bool load_pk = !have_pk || !ctx->pk_loaded || ctx->pk_n != D;
+        const bool load_pk = !have_pk || !ctx->key.loaded || ctx->key.n != D;
         const bool load_ck = !have_ck || !ctx->ck_loaded || ctx->ck_points != D;
         if (load_pk && load_ck) {
             // both keys are uploaded whatever their hashes (a cold call: the
@@ -2307,9 +1612,7 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
                     if (tb.joinable()) tb.join();
                     if (lrc == PNP_OK) {
                         pk_derived = kl.derived;
-                        envelope = !strict || (ctx->pk_qm_zero && ctx->pk_qlookup_zero && !ctx->pk_custom_nz[0] &&
-                                               !ctx->pk_custom_nz[1] && !ctx->pk_custom_nz[2] &&
-                                               !ctx->pk_custom_nz[3] && key_tables_zero(ctx));
+                        envelope = !strict || (!ctx->key.present && key_tables_zero(ctx));
                         ms_pk = ms_since(t);
                         t = clk::now();
                         if (envelope) lrc = pnp_prove(ctx, &circuit, 0, &out);
@@ -2350,15 +1653,13 @@ ProofC gen_proof(CircuitC circuit, ProverKeyC pk, CommitKeyC ck) {
         hp = pk_content_hash(pk, D);
         hc = ck_content_hash(ck, D);
     }
-    if (reload || !have_pk || hp != h_pk || !ctx->pk_loaded || ctx->pk_n != D) {
+    if (reload || !have_pk || hp != h_pk || !ctx->key.loaded || ctx->key.n != D) {
         have_pk = false;
         const auto t_pk = clk::now();
         if ((rc = v1_load_prover_key(ctx, pk, D, kl)) != PNP_OK) die(rc);
         ms_pk_warm = ms_since(t_pk);
         pk_derived = kl.derived;
-        if (strict && (!ctx->pk_qm_zero || !ctx->pk_qlookup_zero || ctx->pk_custom_nz[0] ||
-                       ctx->pk_custom_nz[1] || ctx->pk_custom_nz[2] || ctx->pk_custom_nz[3] ||
-                       !key_tables_zero(ctx))) {
+        if (strict && (ctx->key.present || !key_tables_zero(ctx))) {
             set_error("PNP_V1_STRICT: prover key outside the reference GPU path's envelope (custom-gate "
                       "selectors, q_m, q_lookup or lookup tables non-zero)");
             die(PNP_E_ENVELOPE);

@@ -3,6 +3,7 @@
 // NTT tables, MSM work buffers, a scratch pool and the HBM-resident keys.
 #pragma once
 #include "pnp_internal.h"
+#include "prover_key.h"
 #include <array>
 #include <atomic>
 #include <memory>
@@ -26,55 +27,8 @@ struct pnp_ctx {
     hipStream_t stg_st[kStgThreads] = {};
     hipEvent_t stg_ev[2 * kStgThreads] = {};
 
-    // ---- resident prover key (ProverKeyC mirrored in HBM) ----
-    bool pk_loaded = false;
-    uint64_t pk_n = 0;                     // domain size D
-    std::vector<pnp::DevBuf> pk_owned;     // copies (device_ptrs == 0), by ProverKeyC field
-    ProverKeyC pk_dev{};                   // HBM pointers for every field
-    bool pk_qm_zero = false, pk_qlookup_zero = false;  // all-zero 8n selector evaluations
-    bool pk_custom_nz[4] = {};  // range, logic, fixed-base, curve-add selectors non-zero
-    pnp::DevBuf pk_sigma_n[4];             // sigma evaluations on the n-domain
-    pnp::DevBuf pk_tmp[4];                 // key-load scratch (8n Fr each), kept for the next load
-    // The quotient's 8n-point arrays in block layout (ntt.hip: point 8j + m
-    // -> block m, index j), blocks pk_mb0 .. pk_mb0 + pk_nb - 1 only:
-    // q_* selectors, sig0..3, lin (coset points) and the proof-independent
-    // coset constants computed at key load: vh_inv = v_h^-1 and, when
-    // pk_std_coset (linear_evaluations = 7 w_8n^i, v_h = x^n - 1),
-    // l1v = n^-1 / (x - 1) = L1 / Z_H
-    std::map<std::string, pnp::DevBuf> pk_blk;
-    int pk_mb0 = 0, pk_nb = 8, pk_blk_rank = 0, pk_blk_world = 1;
-    bool pk_std_coset = false;
-    pnp::DevBuf pk_pinv;                   // 1 / (x - w^pos) (block layout), pos = pk_pinv_pos
-    uint64_t pk_pinv_pos = ~0ULL;
-    const uint64_t *blk(const char *name) const {
-        auto it = pk_blk.find(name);
-        return it == pk_blk.end() ? nullptr : it->second.u64();
-    }
-    // the same block arrays in the 2^261 form for k_quotient29 (protocol.h),
-    // made at key load for keys of its class (pk_q29): selectors, sigmas, lin
-    std::map<std::string, pnp::DevBuf> pk_blk29;
-    bool pk_q29 = false;
-    const uint64_t *blk29(const char *name) const {
-        auto it = pk_blk29.find(name);
-        return it == pk_blk29.end() ? nullptr : it->second.u64();
-    }
-    // ---- resident wire map (pnp_preprocess, pnp_load_wire_map) ----
-    // the composer's variable ids of the resident key's circuit: column j (wire
-    // j of every gate) at u32 offset j * wm_gates; pnp_prove_assignment
-    // gathers the witness through it (assignment.hip).  Replaced by the next
-    // preprocess, dropped by any other key load
-    bool wm_loaded = false;
-    uint64_t wm_gates = 0, wm_vars = 0;
-    pnp::DevBuf wm_var;
-    // the row values of q_lookup on the domain (pk_n Fr), from the resident
-    // coefficients when the map became resident; empty: the zero polynomial
-    pnp::DevBuf wm_qlk;
-    void wire_map_drop() {
-        wm_loaded = false;
-        wm_gates = wm_vars = 0;
-        wm_var.release();
-        wm_qlk.release();
-    }
+    // ---- resident prover key and its wire map (prover_key.h) ----
+    pnp::ResidentKey key;
     // ---- resident commit key ----
     bool ck_loaded = false;
     uint64_t ck_points = 0;
@@ -117,7 +71,6 @@ struct pnp_ctx {
         pnp::DevBuf flag;
         uint64_t pk_gen = 0;            // prover-key load the sigma check last covered
     } wb;
-    uint64_t pk_gen = 0;                // incremented by every pnp_load_prover_key
     // the key-load HBM budget (pnp_load_prover_key) left no room for these
     // optional tables: the prover commits without them (same proof bytes)
     // (atomic: the background builder's failure paths set them while a proof
@@ -248,3 +201,15 @@ struct Assignment {
 int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt = nullptr,
                const Assignment *asg = nullptr);
 }  // namespace pnp
+
+// the body of a v2 entry point: codes, never exceptions, across the C ABI
+#define PNP_TRY(...)                                   \
+    try {                                              \
+        __VA_ARGS__;                                   \
+        return PNP_OK;                                 \
+    } catch (const ::pnp::Error &e) {                  \
+        return e.code;                                 \
+    } catch (const std::exception &e) {                \
+        ::pnp::set_error("exception: %s", e.what());   \
+        return PNP_E_DEVICE;                           \
+    }

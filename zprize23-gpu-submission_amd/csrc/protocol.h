@@ -30,7 +30,7 @@ struct QuotArgs {
     const uint64_t *w8[4], *z8, *pi8, *f8, *t8, *h18, *h28, *z28, *l18;
     const uint64_t *q_m, *q_l, *q_r, *q_o, *q_4, *q_c, *q_hl, *q_hr, *q_h4, *q_arith, *q_lookup;
     const uint64_t *sig[4], *lin, *vh_inv;
-    // closed forms on the standard coset (pnp_ctx::pk_std_coset), replacing
+    // closed forms on the standard coset (ResidentKey::std_coset), replacing
     // pi8 / l18: l1v = L1 / Z_H = n^-1 / (x - 1), pinv = 1 / (x - w^pos),
     // PI / Z_H = c_pi * pinv with c_pi = pi * w^pos / n
     const uint64_t *l1v, *pinv;

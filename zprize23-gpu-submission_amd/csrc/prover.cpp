@@ -112,18 +112,18 @@ void div_linear_range(pnp_ctx *ctx, uint64_t *const *d, const Fr *z, int K, uint
 
 int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt,
                const Assignment *asg) {
-    if (!ctx->pk_loaded || !ctx->ck_loaded) {
+    if (!ctx->key.loaded || !ctx->ck_loaded) {
         set_error("prover key / commit key not loaded");
         return PNP_E_NOKEY;
     }
     if (asg) {
-        if (!ctx->wm_loaded) {
+        if (!ctx->key.wm_loaded) {
             set_error("no wire map resident (pnp_preprocess or pnp_load_wire_map first)");
             return PNP_E_NOKEY;
         }
-        if (asg->n_vars != ctx->wm_vars) {
+        if (asg->n_vars != ctx->key.wm_vars) {
             set_error("assignment of %llu variables, the resident wire map has %llu", (unsigned long long)asg->n_vars,
-                      (unsigned long long)ctx->wm_vars);
+                      (unsigned long long)ctx->key.wm_vars);
             return PNP_E_ARG;
         }
     }
@@ -132,13 +132,13 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     PNP_HIP(hipSetDevice(ctx->device));
     // the domain: the circuit's, which must be the key's; an assignment is
     // proved on the key's (its wire map was loaded against it)
-    uint64_t bound = asg ? ctx->pk_n : cs->n > cs->lookup_len ? cs->n : cs->lookup_len;
+    uint64_t bound = asg ? ctx->key.n : cs->n > cs->lookup_len ? cs->n : cs->lookup_len;
     uint64_t n = 1;
     uint32_t lg = 0;
     while (n < bound) { n <<= 1; lg++; }
-    if (n != ctx->pk_n) {
+    if (n != ctx->key.n) {
         set_error("circuit domain %llu != prover key domain %llu", (unsigned long long)n,
-                  (unsigned long long)ctx->pk_n);
+                  (unsigned long long)ctx->key.n);
         return PNP_E_ARG;
     }
     if (ctx->ck_points < n) {
@@ -197,8 +197,8 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         ctx->hbm_checked = true;
     }
     ctx->msm.batch_seq = 0;  // the fixed-slot exchange keys its capacities by batch ordinal
-    const uint64_t N8 = 8 * n, ng = asg ? ctx->wm_gates : cs->n;
-    const ProverKeyC &pk = ctx->pk_dev;
+    const uint64_t N8 = 8 * n, ng = asg ? ctx->key.wm_gates : cs->n;
+    const ProverKeyC &pk = ctx->key.dev;
     Timer tm(ctx);
     auto &nt = ctx->ntt;
     // The proof's algorithmic HBM bytes (the whole-proof GB/s
@@ -215,11 +215,11 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     // round-4 distribution (pnp_set_exchange_a2a, fixed at key load): this
     // rank's coset blocks [mb0, mb0 + nb) and coefficient range [q0, q0 + len)
     const int world = ctx->msm.world;
-    if (ctx->pk_blk_world != world || ctx->pk_blk_rank != ctx->msm.rank) {
+    if (ctx->key.blk_world != world || ctx->key.blk_rank != ctx->msm.rank) {
         set_error("sharding changed after pnp_load_prover_key");
         return PNP_E_ARG;
     }
-    const int mb0 = ctx->pk_mb0, nb = ctx->pk_nb;
+    const int mb0 = ctx->key.mb0, nb = ctx->key.nb;
     const bool dist = nb < 8;
     const uint64_t NB = (uint64_t)nb * n;
     uint64_t q0 = 0, q1 = n;
@@ -253,7 +253,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     // form (the scaled twist, free) and the key arrays it reads are the
     // 2^261-form copies made at key load; any other key keeps k_quotient_
     // (PNP_QUOT29=0: every key)
-    const bool q29 = ctx->pk_q29;
+    const bool q29 = ctx->key.q29;
     auto lde_on = [&](hipStream_t st, const uint64_t *coeffs, uint64_t *dst, bool f29) {
         lde_blocks(nt, coeffs, dst, lg, mb0, nbq, st, f29);
     };
@@ -284,13 +284,13 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
             inputs_h2d = 32.0 * asg->n_vars;
             vals = dv;
         }
-        const uint32_t *var = static_cast<const uint32_t *>(ctx->wm_var.p);
+        const uint32_t *var = static_cast<const uint32_t *>(ctx->key.wm_var.p);
         const uint32_t *dvar[4] = {var, var + ng, var + 2 * ng, var + 3 * ng};
         hipEvent_t e0 = nullptr;
         ctx->ktimer.begin("gather_witness", s, e0);
         k_gather_witness(dvar, ng, vals, asg->n_vars, lg, wsc, s);
         ctx->ktimer.end("gather_witness", s, e0, 16.0 * ng + 4.0 * 32 * ng + 4.0 * 32 * n);
-        if (ctx->wm_qlk.p) qlk = ctx->wm_qlk.u64();
+        if (ctx->key.wm_qlk.p) qlk = ctx->key.wm_qlk.u64();
         else qlk_rows = 0;
         alg(4.0 * (ng / 8.0 + ng + n));  // ids, gathered values, padded columns
     } else {
@@ -433,7 +433,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     (void)sigc;
     for (int j = 0; j < 4; j++) {
         pa.w[j] = wsc[j];
-        pa.sigma[j] = ctx->pk_sigma_n[j].u64();  // NTT.forward(sigma_polys[j]), cached at key load
+        pa.sigma[j] = ctx->key.sigma_n[j].u64();  // NTT.forward(sigma_polys[j]), cached at key load
     }
     const uint64_t kv[4] = {1, 7, 13, 17};  // K1..K3 (permutation/constants.cu:3-15)
     for (int j = 0; j < 4; j++) pa.bk[j] = beta * fr_from_u64(kv[j]);
@@ -496,7 +496,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
     // public input poly (pi.cu:11-15)
     // = iNTT of the evaluations v * e_pos, in closed form: v n^-1 w^(-pos j)
     const Fr n_inv = inverse(fr_from_u64(n));
-    const bool closed = ctx->pk_std_coset;  // L1 (and one PI) on the coset in closed form
+    const bool closed = ctx->key.std_coset;  // L1 (and one PI) on the coset in closed form
     const bool pi_closed = closed && pi_pos.size() == 1;
     uint64_t *pi_poly = nullptr;
     if (pi_pos.size() == 1 && !closed) {
@@ -513,15 +513,15 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         PNP_HIP(hipStreamSynchronize(s));
         ntt_run(nt, pi_poly, lg, true, false, s);
     }
-    if (pi_closed && ctx->pk_pinv_pos != pi_pos[0]) {
+    if (pi_closed && ctx->key.pinv_pos != pi_pos[0]) {
         // 1 / (x_i - w^pos) on this rank's blocks, kept across proofs with the
         // same PI position
-        ctx->pk_pinv_pos = ~0ULL;
-        if (ctx->pk_pinv.bytes < 32 * NB) ctx->pk_pinv.alloc(32 * NB);
+        ctx->key.pinv_pos = ~0ULL;
+        if (ctx->key.pinv.bytes < 32 * NB) ctx->key.pinv.alloc(32 * NB);
         Fr wpos = pow_u64(root_of_unity(lg), pi_pos[0]);
-        k_affine(ctx->pk_pinv.u64(), ctx->blk("lin"), Fr::one(), neg(wpos), NB, s);
-        k_batch_inverse(ctx->pk_pinv.u64(), NB, ctx->scratch_a, s);
-        ctx->pk_pinv_pos = pi_pos[0];
+        k_affine(ctx->key.pinv.u64(), ctx->key.blk[kLin].u64(), Fr::one(), neg(wpos), NB, s);
+        k_batch_inverse(ctx->key.pinv.u64(), NB, ctx->scratch_a, s);
+        ctx->key.pinv_pos = pi_pos[0];
     }
     tm.mark("r3_z2_pi");
 
@@ -551,9 +551,9 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         q.z8 = z8;
         q.pi8 = nullptr;
         q.l18 = q.l1v = q.pinv = nullptr;
-        if (closed) q.l1v = ctx->blk("l1v");
+        if (closed) q.l1v = ctx->key.blk[kL1v].u64();
         if (pi_closed) {
-            q.pinv = ctx->pk_pinv.u64();
+            q.pinv = ctx->key.pinv.u64();
             q.c_pi = pi_val[0] * pow_u64(root_of_unity(lg), pi_pos[0]) * n_inv;
         } else if (pi_poly) {
             uint64_t *pi8 = ctx->buf("pi8", NB);
@@ -595,23 +595,22 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         }
         q.alpha2 = alpha2;
         // prover-key evaluations: block-layout copies made at key load
-        q.q_m = ctx->blk("q_m");  // nullptr = zero selector
-        q.q_l = ctx->blk("q_l");
-        q.q_r = ctx->blk("q_r");
-        q.q_o = ctx->blk("q_o");
-        q.q_4 = ctx->blk("q_4");
-        q.q_c = ctx->blk("q_c");
-        q.q_hl = ctx->blk("q_hl");
-        q.q_hr = ctx->blk("q_hr");
-        q.q_h4 = ctx->blk("q_h4");
-        q.q_arith = ctx->blk("q_arith");
-        q.q_lookup = ctx->blk("q_lookup");
-        q.sig[0] = ctx->blk("sig0");
-        q.sig[1] = ctx->blk("sig1");
-        q.sig[2] = ctx->blk("sig2");
-        q.sig[3] = ctx->blk("sig3");
-        q.lin = ctx->blk("lin");
-        q.vh_inv = ctx->blk("vh_inv");  // v_h^-1, computed at key load
+        auto blk = [&](int r) -> const uint64_t * { return ctx->key.blk[r].u64(); };
+        auto blk29 = [&](int r) -> const uint64_t * { return ctx->key.blk29[r].u64(); };
+        q.q_m = blk(kQm);  // nullptr = zero selector
+        q.q_l = blk(kQl);
+        q.q_r = blk(kQr);
+        q.q_o = blk(kQo);
+        q.q_4 = blk(kQ4);
+        q.q_c = blk(kQc);
+        q.q_hl = blk(kQhl);
+        q.q_hr = blk(kQhr);
+        q.q_h4 = blk(kQh4);
+        q.q_arith = blk(kQarith);
+        q.q_lookup = blk(kQlookup);
+        for (int j = 0; j < 4; j++) q.sig[j] = blk(kSig0 + j);
+        q.lin = blk(kLin);
+        q.vh_inv = blk(kVhInv);  // v_h^-1, computed at key load
         q.n = n;
         q.lg_n = lg;
         q.alpha = alpha;
@@ -645,18 +644,18 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
             for (int j = 0; j < 4; j++) q2.w8[j] = q.w8[j];
             q2.z8 = q.z8;
             q2.pi8 = q.pi8;
-            q2.q_m = ctx->blk29("q_m");
-            q2.q_l = ctx->blk29("q_l");
-            q2.q_r = ctx->blk29("q_r");
-            q2.q_o = ctx->blk29("q_o");
-            q2.q_4 = ctx->blk29("q_4");
-            q2.q_c = ctx->blk29("q_c");
-            q2.q_hl = ctx->blk29("q_hl");
-            q2.q_hr = ctx->blk29("q_hr");
-            q2.q_h4 = ctx->blk29("q_h4");
-            q2.q_arith = ctx->blk29("q_arith");
-            for (int j = 0; j < 4; j++) q2.sig[j] = ctx->blk29(("sig" + std::to_string(j)).c_str());
-            q2.lin = ctx->blk29("lin");
+            q2.q_m = blk29(kQm);
+            q2.q_l = blk29(kQl);
+            q2.q_r = blk29(kQr);
+            q2.q_o = blk29(kQo);
+            q2.q_4 = blk29(kQ4);
+            q2.q_c = blk29(kQc);
+            q2.q_hl = blk29(kQhl);
+            q2.q_hr = blk29(kQhr);
+            q2.q_h4 = blk29(kQh4);
+            q2.q_arith = blk29(kQarith);
+            for (int j = 0; j < 4; j++) q2.sig[j] = blk29(kSig0 + j);
+            q2.lin = blk29(kLin);
             q2.vh_inv = q.vh_inv;
             q2.l1v = q.l1v;
             q2.pinv = q.pinv;
@@ -687,17 +686,14 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         } else {
             k_quotient(q, NBq, t_blk, s);
         }
-        if (ctx->pk_custom_nz[0] || ctx->pk_custom_nz[1] || ctx->pk_custom_nz[2] || ctx->pk_custom_nz[3]) {
+        if (ctx->key.any_custom()) {
             WidgetArgs g;
             for (int j = 0; j < 4; j++) g.w8[j] = q.w8[j];
             g.q_l = q.q_l;
             g.q_r = q.q_r;
             g.q_c = q.q_c;
             g.vh_inv = q.vh_inv;
-            g.sel[0] = ctx->blk("range");
-            g.sel[1] = ctx->blk("logic");
-            g.sel[2] = ctx->blk("fixed_add");
-            g.sel[3] = ctx->blk("var_add");
+            for (int k = 0; k < 4; k++) g.sel[k] = blk(kRange + k);  // range, logic, fixed-base, curve-add
             g.sep[0] = range_c;
             g.sep[1] = logic_c;
             g.sep[2] = fixed_c;
@@ -858,7 +854,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
             if (!z2_one) k_poly_eval(z2_poly, n, zw, ctx->scratch_a, &z2n, s);
             Fr f_eval = Fr::zero(), t_eval = Fr::zero(), t_next = Fr::zero();
             Fr ql_eval = Fr::zero(), h1_eval = Fr::zero(), h1_next = Fr::zero(), h2_eval = Fr::zero();
-            if (!ctx->pk_qlookup_zero) k_poly_eval(pk.q_lookup_coeffs, n, zc, ctx->scratch_a, &ql_eval, s);
+            if (!ctx->key.qlookup_zero()) k_poly_eval(pk.q_lookup_coeffs, n, zc, ctx->scratch_a, &ql_eval, s);
             if (!h_zero) {
                 k_poly_eval(h1_poly, n, zc, ctx->scratch_a, &h1_eval, s);
                 k_poly_eval(h1_poly, n, zw, ctx->scratch_a, &h1_next, s);
@@ -914,7 +910,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         auto push = [&](const uint64_t *p, const Fr &sc) { push_local(p + 4 * q0, sc); };
         auto p5 = [](const Fr &x) { Fr x2 = x * x; return x2 * x2 * x; };
         // arithmetic (widget/arithmetic.rs:82-100)
-        if (!ctx->pk_qm_zero) push(pk.q_m_coeffs, ae * be * qae);
+        if (!ctx->key.qm_zero()) push(pk.q_m_coeffs, ae * be * qae);
         push(pk.q_l_coeffs, ae * qae);
         push(pk.q_r_coeffs, be * qae);
         push(pk.q_o_coeffs, ce * qae);
@@ -937,10 +933,10 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
             wv.q_l = ld(ce_->q_l_eval);
             wv.q_r = ld(ce_->q_r_eval);
             wv.q_c = ld(ce_->q_c_eval);
-            if (ctx->pk_custom_nz[0]) push(pk.range_selector_coeffs, w_range(range_c, wv));
-            if (ctx->pk_custom_nz[1]) push(pk.logic_selector_coeffs, w_logic(logic_c, wv));
-            if (ctx->pk_custom_nz[2]) push(pk.fixed_group_add_selector_coeffs, w_fbsm(fixed_c, wv));
-            if (ctx->pk_custom_nz[3]) push(pk.variable_group_add_selector_coeffs, w_cadd(var_c, wv));
+            if (ctx->key.custom(0)) push(pk.range_selector_coeffs, w_range(range_c, wv));
+            if (ctx->key.custom(1)) push(pk.logic_selector_coeffs, w_logic(logic_c, wv));
+            if (ctx->key.custom(2)) push(pk.fixed_group_add_selector_coeffs, w_fbsm(fixed_c, wv));
+            if (ctx->key.custom(3)) push(pk.variable_group_add_selector_coeffs, w_cadd(var_c, wv));
         }
         // compute_linearisation_permutation (proof_system/permutation.cu:231-265)
         {
@@ -958,7 +954,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         {
             const LookupEvaluationsC *lk = &ev->lookup_evals;
             Fr sep2 = lsep * lsep, sep3 = sep2 * lsep, opd = delta + Fr::one(), eopd = eps * opd;
-            if (!ctx->pk_qlookup_zero) {
+            if (!ctx->key.qlookup_zero()) {
                 Fr ct = ((de * zeta + ce) * zeta + be) * zeta + ae;
                 push(pk.q_lookup_coeffs, (ct - ld(lk->f_eval)) * lsep);
             }

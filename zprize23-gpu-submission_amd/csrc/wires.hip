@@ -294,7 +294,7 @@ void build_wire_bases(pnp_ctx *ctx, uint64_t n) {
     wb = pnp_ctx::WireBases{};
     wb.built = true;
     wb.n = n;
-    wb.pk_gen = ctx->pk_gen;
+    wb.pk_gen = ctx->key.gen;
     uint32_t lg = 0;
     while ((1ULL << lg) < n) lg++;
     const uint64_t N = 4 * n;
@@ -304,7 +304,7 @@ void build_wire_bases(pnp_ctx *ctx, uint64_t n) {
     // the sigma evaluations this build reads, kept to recognise the key later
     wb.sigma.alloc(N * 32);
     for (int j = 0; j < 4; j++)
-        PNP_HIP(hipMemcpyAsync(wb.sigma.u64() + 4 * (uint64_t)j * n, ctx->pk_sigma_n[j].u64(), n * 32,
+        PNP_HIP(hipMemcpyAsync(wb.sigma.u64() + 4 * (uint64_t)j * n, ctx->key.sigma_n[j].u64(), n * 32,
                                hipMemcpyDeviceToDevice, s));
     // 1. successor of every position
     DevBuf next(N * 4), lab(N * 4);
@@ -510,16 +510,16 @@ void build_wire_bases(pnp_ctx *ctx, uint64_t n) {
 bool wire_bases_ready(pnp_ctx *ctx, uint64_t n) {
     if (tables_busy(ctx)) return false;  // being built in the background: commit without them
     auto &wb = ctx->wb;
-    if (wb.built && wb.n == n && wb.pk_gen != ctx->pk_gen) {
+    if (wb.built && wb.n == n && wb.pk_gen != ctx->key.gen) {
         // the prover key was loaded again (the v1 symbol does it every call):
         // same sigma, same groups
         DevBuf own;  // (the builder's thread keeps off the proof's scratch)
         DevBuf &scr = t_bg_build ? own : ctx->scratch_b;
         bool same = wb.sigma.p != nullptr;
         for (int j = 0; j < 4 && same; j++)
-            same = !k_any_diff(wb.sigma.u64() + 4 * (uint64_t)j * n, ctx->pk_sigma_n[j].u64(), 4 * n, scr,
+            same = !k_any_diff(wb.sigma.u64() + 4 * (uint64_t)j * n, ctx->key.sigma_n[j].u64(), 4 * n, scr,
                                tables_stream(ctx));
-        if (same) wb.pk_gen = ctx->pk_gen;
+        if (same) wb.pk_gen = ctx->key.gen;
         else wb.built = false;
     }
     // a deferring proof goes without them (built in the background or by the next proof)
@@ -542,7 +542,7 @@ bool wire_bases_ready(pnp_ctx *ctx, uint64_t n) {
             ctx->wb = pnp_ctx::WireBases{};
             wb.built = true;
             wb.n = n;
-            wb.pk_gen = ctx->pk_gen;
+            wb.pk_gen = ctx->key.gen;
             ctx->hbm_groups_off = true;
         } else if (ctx->msm.world > 1) {  // the ranks' verdicts come from the same key: check they agree
             const bool w = all_ranks_ok(ctx, wb.wires_ok), z = all_ranks_ok(ctx, wb.z_ok);
