@@ -1,9 +1,9 @@
-"""Model of the radix-2^29 Fr arithmetic of the NTT passes (csrc/fr29.cuh,
+"""Model of the radix-2^29 Fr arithmetic (csrc/fr29.cuh: the quotient kernel's,
 constants tools/gen_fr29.py -> csrc/fr29_consts.inc): every operation mirrors
 the device code limb for limb and asserts the bounds the device code relies on
 (u32 limbs, u64 column sums, the value bounds of a DIF / DIT pass of up to 8
 levels from canonical inputs).  The device kernels themselves are checked
-against the oracle by the GPU NTT / LDE / proof tests."""
+against the oracle by the GPU proof tests."""
 import os
 import random
 import re
@@ -131,7 +131,7 @@ def test_constants():
         assert val(C["KDIF"][lv]) == R << (lv + 1)
     assert val(C["R29_KDIT"]) == 4 * R
     assert val(C["R29_C266"]) == 2**266 % R
-    # a 2^256-form table entry -> 2^261 form (ntt.hip k_table_to_r29)
+    # a 2^256-form table entry -> 2^261 form
     v = 0x1234567 * 2**256 % R
     assert val(canon(mul(limbs(v), C["R29_C266"]))) == v * 32 % R
 

@@ -2,7 +2,7 @@
 #   bash tools/abn.sh <rounds> <variant> ...
 # variant: "base" (the in-tree build), a library path (PNP_PLONK_LIB), or
 # VAR=value (an environment setting for the in-tree build), several of them
-# joined by '@' (e.g. PNP_MSM_PIPE=1@PNP_PLONK_LIB=lib_var/x/libpnp_plonk.so); ABN_ARGS: extra
+# joined by '@' (e.g. PNP_NTT_ROWS=0@PNP_PLONK_LIB=lib_var/x/libpnp_plonk.so); ABN_ARGS: extra
 # bench.py arguments for every run (e.g. "--solo 0/8"); ABN_OUT: where the
 # runs' JSON lines and logs go (default ab_out/).  Every run checks its proof
 # (bench.py --full without the CPU baseline and the drop-in lines)

@@ -418,20 +418,13 @@ HbmPlan hbm_plan(pnp_ctx *ctx, uint64_t n) {
                                 NB * (8 + (lookups ? 4 : 0) + (closed ? 0 : 2)) + std::max(n, NB) * 9 / 8);
     const uint64_t work_held = map_bytes(ctx->work) + ctx->scratch_a.bytes + ctx->scratch_b.bytes + ctx->key.pinv.bytes;
     // NTT tables: twiddles of n (both directions), the block twists (forward,
-    // inverse, x32) of the 8n coset; with PNP_NTT29 their 2^261 forms
-    static const bool ntt29 = [] {
-        const char *e = getenv("PNP_NTT29");
-        return e && atoi(e) != 0;
-    }();
+    // inverse, x32) of the 8n coset
     // (+ the dense twiddle rows of both directions, 2 x (n - 1) entries)
-    const uint64_t ntt = 32 * n + 64 * n + 3 * 32 * N8 + (ntt29 ? 36 * n / 2 * 2 + 3 * 36 * N8 : 0);
+    const uint64_t ntt = 32 * n + 64 * n + 3 * 32 * N8;
     // (the 8n LDE twist of pnp_coset_lde8 is not a proof's: not counted as held)
     const uint64_t ntt_held = map_bytes(ctx->ntt.fwd) + map_bytes(ctx->ntt.inv) + map_bytes(ctx->ntt.fwd_rows) +
                               map_bytes(ctx->ntt.inv_rows) + map_bytes(ctx->ntt.blk_twist) +
-                              map_bytes(ctx->ntt.blk_twist_inv) + map_bytes(ctx->ntt.fwd29) +
-                              map_bytes(ctx->ntt.inv29) + map_bytes(ctx->ntt.blk_twist29) +
-                              map_bytes(ctx->ntt.blk_twist_inv29) + map_bytes(ctx->ntt.blk_twist32) +
-                              map_bytes(ctx->ntt.blk_twist32_29);
+                              map_bytes(ctx->ntt.blk_twist_inv) + map_bytes(ctx->ntt.blk_twist32);
     const uint64_t ck_tab = msm_table_bytes(n_tab, n, wk.fold_c);
     const uint64_t msm = msm_work_bytes(per, n, wk.fold_c, 9, wk.v_bytes, world);
     const uint64_t held = work_held + ntt_held + ctx->ck_table.bytes + msm_work_held(wk);
@@ -667,12 +660,6 @@ void pnp_ctx_destroy(pnp_ctx *ctx) {
     if (ctx->bg_stream) (void)hipStreamDestroy(ctx->bg_stream);
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->msm.s2) {
-        (void)hipStreamSynchronize(ctx->msm.s2);
-        (void)hipStreamDestroy(ctx->msm.s2);
-    }
-    for (hipEvent_t e : ctx->msm.ev)
-        if (e) (void)hipEventDestroy(e);
     if (ctx->stream_lo) {
         (void)hipStreamSynchronize(ctx->stream_lo);
         (void)hipStreamDestroy(ctx->stream_lo);

@@ -1,5 +1,8 @@
-// fr29.cuh — BLS12-381 Fr in radix 2^29 (nine limbs) for the NTT passes on
-// gfx950.
+// fr29.cuh — BLS12-381 Fr in radix 2^29 (nine limbs) on gfx950: the
+// arithmetic of the round-4 quotient (protocol.hip k_quotient29).  It was
+// written for NTT passes, which were measured slower than the 32-bit ones and
+// removed; the pass bounds below are what
+// tests/test_fr29.py still models.
 //
 // Why: the 32-bit-limb product (field.cuh) pairs every v_mad_u64_u32 with a
 // v_addc_co_u32 to carry the column sums, and its add / sub / select chains run
@@ -11,7 +14,7 @@
 // Representation: value = sum l_i 2^(29 i), l_0..l_7 < 2^29, the top limb
 // l_8 < 2^32 holds everything above bit 232 (values < 2^264).  The data keep
 // the HBM form's Montgomery factor (2^256, field.cuh); twiddles and twist
-// factors are stored times 2^261 (tables built by ntt.hip), so r29_mul
+// factors are stored times 2^261, so r29_mul
 // (x y 2^-261) maps data to data.  Nothing is reduced inside a pass: a DIF
 // level doubles the bound (a + b), a difference adds a multiple of r with
 // lifted limbs (no borrows), a product is < x y / 2^261 + r; r29_canon brings

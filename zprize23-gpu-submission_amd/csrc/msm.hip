@@ -282,25 +282,9 @@ static void scan_u32(uint32_t *d, uint64_t n, DevBuf &scratch, hipStream_t s) {
 #ifndef PNP_TILE_K
 #define PNP_TILE_K 16384
 #endif
-// the next tile's loads issued before this tile's LDS phases (both passes)
-#ifndef PNP_SORT_PREFETCH
-#define PNP_SORT_PREFETCH 1
-#endif
 constexpr int TILE_K = PNP_TILE_K;
 constexpr int KPT = TILE_K / 1024;  // keys per lane per tile
 static_assert(TILE_K % 4096 == 0 && TILE_K <= 16384, "PNP_TILE_K: a multiple of 4096 up to 16384");
-// exclusive scan of lh[0..nb) into lofs by the whole workgroup: each lane
-// sums its run of ceil(nb / blockDim) bins, one wave-level scan, the wave
-// totals through LDS (wsum: blockDim / 64 words).  Every lane must call it; the
-// caller synchronises after it.  (PNP_SORT_SCAN=0: wave 0 alone, 32 bins per
-// lane in sequence at 2048 fine bins while 15 waves wait at the barrier)
-// (PNP_SORT_SCAN=1: the wave scan by __shfl_up, ds_bpermute through the LDS
-// crossbar, and the wave totals summed one LDS read after another; 2: DPP
-// row shifts / broadcasts in the VALU, and the totals of the <= 16 waves read
-// once per lane and scanned the same way)
-#ifndef PNP_SORT_SCAN
-#define PNP_SORT_SCAN 2
-#endif
 // inclusive scan over the 64 lanes of a wave by DPP: row_shr 1, 2, 4, 8 inside
 // each row of 16 lanes, then row_bcast:15 and row_bcast:31 carry the row totals
 __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
@@ -319,14 +303,15 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
     if (lane >= 32) x += t;
     return x;
 }
-__device__ __forceinline__ void tile_scan_wave0(uint32_t *lh, uint32_t *lofs, int nb);
+// exclusive scan of lh[0..nb) into lofs by the whole workgroup: each lane
+// sums its run of ceil(nb / blockDim) bins, one wave-level scan, the wave
+// totals through LDS (wsum: blockDim / 64 words).  Every lane must call it; the
+// caller synchronises after it.
 __device__ __forceinline__ void tile_scan(uint32_t *lh, uint32_t *lofs, int nb, uint32_t *wsum) {
-#if PNP_SORT_SCAN
     const int per = (nb + (int)blockDim.x - 1) / (int)blockDim.x, b0 = (int)threadIdx.x * per;
     uint32_t loc = 0;
     for (int b = b0; b < b0 + per && b < nb; b++) loc += lh[b];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#if PNP_SORT_SCAN == 2
     const uint32_t x = wave_scan_incl(loc);
     if (lane == 63) wsum[wv] = x;
     __syncthreads();
@@ -335,58 +320,14 @@ __device__ __forceinline__ void tile_scan(uint32_t *lh, uint32_t *lofs, int nb, 
     const uint32_t wt = wave_scan_incl(lane < nw ? wsum[lane] : 0u);
     const int wsrc = __builtin_amdgcn_readfirstlane(wv) - 1;
     uint32_t run = x - loc + (wsrc >= 0 ? (uint32_t)__builtin_amdgcn_readlane((int)wt, wsrc) : 0u);
-#else
-    uint32_t x = loc;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) wsum[wv] = x;
-    __syncthreads();
-    uint32_t run = x - loc;
-    for (int j = 0; j < wv; j++) run += wsum[j];
-#endif
     for (int b = b0; b < b0 + per && b < nb; b++) {
         lofs[b] = run;
         run += lh[b];
     }
-#else
-    (void)wsum;
-    tile_scan_wave0(lh, lofs, nb);
-#endif
-}
-__device__ __forceinline__ void tile_scan_wave0(uint32_t *lh, uint32_t *lofs, int nb) {
-    // exclusive scan of lh[0..nb) into lofs by wave 0
-    if (threadIdx.x < 64) {
-        const int per = (nb + 63) / 64, b0 = threadIdx.x * per;
-        uint32_t loc = 0;
-        for (int b = b0; b < b0 + per && b < nb; b++) loc += lh[b];
-        uint32_t x = loc;
-        for (int off = 1; off < 64; off <<= 1) {
-            uint32_t y = __shfl_up(x, off, 64);
-            if ((int)threadIdx.x >= off) x += y;
-        }
-        uint32_t run = x - loc;
-        for (int b = b0; b < b0 + per && b < nb; b++) {
-            lofs[b] = run;
-            run += lh[b];
-        }
-    }
 }
 
-// Tile ranking of pass A.  PNP_SORT_WAVERANK=0: one LDS atomic-with-return per
-// key on the tile's bin counters.  1: wave-level ranking —
-// each wave keeps its own 16-bit bin counters; a key's peers in its wave (same
-// bin) come from one ballot per bin bit (match-any), its rank is the popcount of
-// the peers below it (mbcnt), and the lowest peer alone adds the group to the
-// wave's counter (a plain LDS read and write: a wave's LDS operations execute in
-// order, so no atomic); the tile's bin offsets are then one scan over
-// (bin, wave) in bin-major order, which also makes the tile's order stable
-#ifndef PNP_SORT_WAVERANK
-#define PNP_SORT_WAVERANK 0
-#endif
-constexpr int SORT_NW = 16;  // waves of a 1024-lane sort workgroup
-
+// Tile ranking of pass A: one LDS atomic-with-return per key on the tile's
+// bin counters.
 // rec != nullptr: entries leave as 8-byte records entry | fine key << 32 (the
 // bucket-range exchange format) instead of the ent / fk arrays.  slot_recs > 0
 // (fixed-slot exchange): destination d's records go to its slot, rec + d
@@ -401,15 +342,6 @@ __global__ __launch_bounds__(1024) void k_coarse_scatter(const uint32_t *keys, K
     __shared__ uint32_t cur[1 << SORT_CB], lh[1 << SORT_CB], lofs[1 << SORT_CB], lim[1 << SORT_CB], wsum[16];
     __shared__ uint32_t st_e[TILE_K];
     __shared__ uint32_t st_m[TILE_K];
-#if PNP_SORT_WAVERANK
-    // per-wave bin counters (<= KPT * 64 per wave), then the (bin, wave) offsets
-    __shared__ uint16_t wh[SORT_NW][1 << SORT_CB];
-    __shared__ uint32_t tile_total;
-    const int cbits = 31 - __builtin_clz((uint32_t)NBc);
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t below = (1ULL << lane) - 1;
-    for (int b = threadIdx.x; b < SORT_NW * NBc; b += blockDim.x) wh[b / NBc][b % NBc] = 0;
-#endif
     const int v = blockIdx.y, ch = blockIdx.x;
     for (int b = threadIdx.x; b < NBc; b += blockDim.x) {
         cur[b] = offs[cidx(v, gridDim.y, b, NBc, wmaj, ch, nch)];
@@ -463,62 +395,7 @@ __global__ __launch_bounds__(1024) void k_coarse_scatter(const uint32_t *keys, K
             uint32_t key[KPT], rank[KPT];
 #pragma unroll
             for (int j = 0; j < KPT; j++) key[j] = nxt[j];
-#if PNP_SORT_PREFETCH
             if (nr < kr.rows) load_tile(nr, ntb, nxt);
-#endif
-#if PNP_SORT_WAVERANK
-#pragma unroll
-            for (int j = 0; j < KPT; j++) {
-                const bool valid = key[j] != KEY_ZERO;
-                const uint32_t bin = valid ? (key[j] & 0x7FFFFFFFu) >> fb : 0u;
-                uint64_t peers = __ballot(valid);
-                for (int b = 0; b < cbits; b++) {
-                    const bool bit = (bin >> b) & 1u;
-                    const uint64_t m = __ballot(bit);
-                    peers &= bit ? m : ~m;
-                }
-                if (valid) {
-                    const uint32_t base = wh[wv][bin];
-                    rank[j] = base + (uint32_t)__popcll(peers & below);
-                    if ((peers & below) == 0) wh[wv][bin] = (uint16_t)(base + (uint32_t)__popcll(peers));
-                }
-            }
-            __syncthreads();
-            {
-                // exclusive scan of the (bin, wave) counters in bin-major order
-                const int E = SORT_NW * NBc, per = (E + (int)blockDim.x - 1) / (int)blockDim.x;
-                const int f0 = (int)threadIdx.x * per;
-                uint32_t loc = 0;
-                for (int f = f0; f < f0 + per && f < E; f++) loc += wh[f % SORT_NW][f / SORT_NW];
-                const uint32_t x = wave_scan_incl(loc);
-                if (lane == 63) wsum[wv] = x;
-                __syncthreads();
-                const uint32_t wt = wave_scan_incl(lane < SORT_NW ? wsum[lane] : 0u);
-                const int wsrc = __builtin_amdgcn_readfirstlane(wv) - 1;
-                uint32_t run = x - loc + (wsrc >= 0 ? (uint32_t)__builtin_amdgcn_readlane((int)wt, wsrc) : 0u);
-                if (threadIdx.x == blockDim.x - 1) tile_total = run + loc;
-                for (int f = f0; f < f0 + per && f < E; f++) {
-                    const int b = f / SORT_NW, w = f % SORT_NW;
-                    const uint32_t c = wh[w][b];
-                    if (w == 0) lofs[b] = run;
-                    wh[w][b] = (uint16_t)run;
-                    run += c;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < KPT; j++) {
-                if (key[j] == KEY_ZERO) continue;
-                const uint64_t i = tb + 4 * (threadIdx.x + 1024 * (j / 4)) + (j & 3);
-                uint32_t mag = key[j] & 0x7FFFFFFFu, at = wh[wv][mag >> fb] + rank[j];
-                st_e[at] = (idb + (uint32_t)i) | (key[j] & 0x80000000u);
-                st_m[at] = mag;
-            }
-            __syncthreads();
-            const uint32_t total = tile_total;
-            for (int b = threadIdx.x; b < NBc; b += blockDim.x)
-                lh[b] = (b + 1 < NBc ? lofs[b + 1] : total) - lofs[b];
-#else
 #pragma unroll
             for (int j = 0; j < KPT; j++)
                 if (key[j] != KEY_ZERO) rank[j] = atomicAdd(&lh[(key[j] & 0x7FFFFFFFu) >> fb], 1u);
@@ -535,7 +412,6 @@ __global__ __launch_bounds__(1024) void k_coarse_scatter(const uint32_t *keys, K
             }
             __syncthreads();
             const uint32_t total = lofs[NBc - 1] + lh[NBc - 1];
-#endif
             for (uint32_t x = threadIdx.x; x < total; x += blockDim.x) {
                 uint32_t mag = st_m[x], bn = mag >> fb;
                 uint32_t pos = cur[bn] + x - lofs[bn];
@@ -551,14 +427,8 @@ __global__ __launch_bounds__(1024) void k_coarse_scatter(const uint32_t *keys, K
                 cur[b] += lh[b];
                 lh[b] = 0;
             }
-#if PNP_SORT_WAVERANK
-            for (int b = threadIdx.x; b < SORT_NW * NBc; b += blockDim.x) wh[b / NBc][b % NBc] = 0;
-#endif
             __syncthreads();
         }
-#if !PNP_SORT_PREFETCH
-        if (nr < kr.rows) load_tile(nr, ntb, nxt);
-#endif
         r = nr, tb = ntb;
     }
 }
@@ -643,10 +513,8 @@ __global__ __launch_bounds__(1024) void k_fine_sort(const uint32_t *ent, const u
         uint32_t f[PER];
 #pragma unroll
         for (int j = 0; j < PER; j++) e[j] = ne[j], f[j] = nf[j];
-#if PNP_SORT_PREFETCH
         // in flight through this tile's LDS phases (the barriers wait for LDS only)
         if (pe - tb > (uint32_t)TILE_F) load_tile(tb + TILE_F);
-#endif
 #pragma unroll
         for (int j = 0; j < PER; j++)
             if (tb + threadIdx.x + j * 1024 < pe) rank[j] = atomicAdd(&lh[f[j]], 1u);
@@ -674,9 +542,6 @@ __global__ __launch_bounds__(1024) void k_fine_sort(const uint32_t *ent, const u
             lh[q] = 0;
         }
         __syncthreads();
-#if !PNP_SORT_PREFETCH
-        if (pe - tb > (uint32_t)TILE_F) load_tile(tb + TILE_F);
-#endif
     }
 }
 
@@ -949,31 +814,19 @@ __global__ __launch_bounds__(256) void k_accumulate_flat(const uint64_t *points,
 // stored coordinates < 2^389, every product input < 2^391 (Y3 < 2^382 comes
 // from mul2_29).  No equal /
 // opposite / infinity cases: those make ZZ = 0 mod q, detected per piece.
-// PNP_F29_KARA=1: the Karatsuba a*b halves (field29.cuh mul29k / mul2_29k, 13%
-// fewer multiply-adds, same issue cycles; A/B in DESIGN.md)
-#ifndef PNP_F29_KARA
-#define PNP_F29_KARA 0
-#endif
-#if PNP_F29_KARA
-#define MUL29 mul29k
-#define MUL2_29 mul2_29k
-#else
-#define MUL29 mul29
-#define MUL2_29 mul2_29
-#endif
 __device__ __forceinline__ void madd29(Xyzz29 &p, const F29 &x2, const F29 &y2) {
-    F29 u2 = MUL29(x2, p.zz);
-    F29 s2 = MUL29(y2, p.zzz);
+    F29 u2 = mul29(x2, p.zz);
+    F29 s2 = mul29(y2, p.zzz);
     F29 P = sub29(u2, p.x, F29_KB);
     F29 R = sub29(s2, p.y, F29_KB);
     F29 pp = sqr29(P);
-    F29 ppp = MUL29(P, pp);
-    F29 q = MUL29(p.x, pp);
+    F29 ppp = mul29(P, pp);
+    F29 q = mul29(p.x, pp);
     F29 x3 = sub29(sub29(sub29(sqr29(R), ppp, F29_KA), q, F29_KA), q, F29_KA);
     // Y3 = R (Q - X3) - Y PPP as R (Q - X3) + Y (KA - PPP), one reduction
-    F29 y3 = MUL2_29(R, sub29(q, x3, F29_KB), p.y, neg29(ppp, F29_KA));
-    p.zz = MUL29(p.zz, pp);
-    p.zzz = MUL29(p.zzz, ppp);
+    F29 y3 = mul2_29(R, sub29(q, x3, F29_KB), p.y, neg29(ppp, F29_KA));
+    p.zz = mul29(p.zz, pp);
+    p.zzz = mul29(p.zzz, ppp);
     p.x = x3;
     p.y = y3;
 }
@@ -1000,15 +853,12 @@ __device__ __forceinline__ bool store29(uint32_t *dst, const Xyzz29 &p) {
 #endif
 static constexpr uint64_t PT29 = PNP_PT29;
 
-// Gather staging (PNP_ACC_GLDS): the next entry's point (7 x 16 B per lane) is
+// Gather staging: the next entry's point (7 x 16 B per lane) is
 // fetched global -> LDS by global_load_lds_dwordx4 while the current entry is
 // added, so the ~us gather latency hides behind the addition without holding
 // 28 more VGPRs (register prefetch spilled at the 3-wave budget).  Each wave
 // owns 7 KiB of LDS: chunk c of lane l at stage[wave][c][l] (lane-linear, as
 // the LDS-DMA destination requires).
-#ifndef PNP_ACC_GLDS
-#define PNP_ACC_GLDS 1
-#endif
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void glob_void_t;
 __device__ __forceinline__ void stage_point(const uint32_t *p, uint4 *st) {
@@ -1034,11 +884,10 @@ __device__ __forceinline__ void unstage_point(const uint4 *st, F29 &x, F29 &y) {
 }
 
 __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint32_t *pts29, const uint32_t *sorted,
-                                                      const uint32_t *offs, uint64_t U, uint64_t nthr, uint32_t S,
+                                                      const uint32_t *offs, uint64_t U, uint32_t S,
                                                       uint32_t *buckets, uint32_t *head,
                                                       uint32_t *tail, uint32_t *tailb, uint32_t *redo,
                                                       uint32_t *nredo, uint32_t *tlist) {
-#if PNP_ACC_GLDS == 1
     // per wave: the staged point (7 x 64 x 16 B) and the staged next index
     // (64 x 4 B); both arrive by LDS-DMA, so no ordinary global load result is
     // consumed inside the loop (that would make the compiler drain the DMA)
@@ -1047,10 +896,8 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
     const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     uint4 *wave_base = stage + 7 * 64 * wv;
     uint32_t *idx_base = sidx + 64 * wv;
-#endif
     uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     const uint32_t total = offs[U];
-    S = acc_seg(offs, U, nthr, S);
     const uint64_t lo64 = t * S;
     if (lo64 >= total) return;
     const uint32_t lo = (uint32_t)lo64;
@@ -1065,17 +912,10 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
     uint32_t next = offs[cur + 1];
     bool ok = true, fresh = true;
     Xyzz29 acc;
-#if PNP_ACC_GLDS == 1
     uint32_t e = sorted[lo];
     stage_point(pts29 + PT29 * (e & 0x7FFFFFFFu), wave_base);
     if (lo + 1 < hi)
         __builtin_amdgcn_global_load_lds((glob_void_t *)(sorted + lo + 1), (lds_void_t *)idx_base, 4, 0, 0);
-#elif PNP_ACC_GLDS == 2
-    // (2: the next point prefetched into registers, the index after it too)
-    uint32_t e = sorted[lo];
-    F29 nx = load29(pts29 + PT29 * (e & 0x7FFFFFFFu)), ny = load29(pts29 + PT29 * (e & 0x7FFFFFFFu) + 14);
-    uint32_t en = lo + 1 < hi ? sorted[lo + 1] : 0u;
-#endif
     for (uint32_t k = lo; k < hi; k++) {
         if (k == next) {
             ok &= store29(first ? head + 56 * t : buckets + 56 * cur, acc);
@@ -1083,18 +923,6 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
             fresh = true;
             cur = next_bucket(offs, 1, U, cur + 1, k, next);
         }
-#if PNP_ACC_GLDS == 2
-        F29 x = nx, y = ny;
-        const uint32_t ecur = e;
-        if (k + 1 < hi) {
-            const uint32_t *p = pts29 + PT29 * (en & 0x7FFFFFFFu);
-            nx = load29(p);
-            ny = load29(p + 14);
-            e = en;
-            if (k + 2 < hi) en = sorted[k + 2];
-        }
-        if (ecur >> 31) y = neg29(y, F29_KA);
-#elif PNP_ACC_GLDS
         F29 x, y;
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): point k and index k+1 have landed
         unstage_point(wave_base + ln, x, y);
@@ -1109,12 +937,6 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
             e = en;
         }
         if (ecur >> 31) y = neg29(y, F29_KA);
-#else
-        const uint32_t e = sorted[k];
-        const uint32_t *p = pts29 + PT29 * (e & 0x7FFFFFFFu);
-        F29 x = load29(p), y = load29(p + 14);
-        if (e >> 31) y = neg29(y, F29_KA);
-#endif
         if (fresh) {
             acc.x = x;
             acc.y = y;
@@ -1153,9 +975,8 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
 // the ~2M-bucket launch takes microseconds, not the ~0.3 ms one contended
 // counter cost); the host sums them.
 constexpr int WCTR_SLOTS = 64;
-__global__ __launch_bounds__(1024) void k_count_pieces(const uint32_t *offs, uint64_t WB, uint64_t nthr, uint32_t S,
+__global__ __launch_bounds__(1024) void k_count_pieces(const uint32_t *offs, uint64_t WB, uint32_t S,
                                                        unsigned long long *ctr) {
-    S = acc_seg(offs, WB, nthr, S);
     __shared__ uint32_t part[16];
     const uint64_t b = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     bool fresh = false;
@@ -1180,7 +1001,7 @@ __global__ __launch_bounds__(1024) void k_count_pieces(const uint32_t *offs, uin
 
 // exact 32-bit recomputation of the segments k_accumulate29 flagged
 __global__ __launch_bounds__(64) void k_accumulate_redo(const uint32_t *pts29, const uint32_t *sorted,
-                                                        const uint32_t *offs, uint64_t U, uint64_t nthr, uint32_t S,
+                                                        const uint32_t *offs, uint64_t U, uint32_t S,
                                                         uint32_t *buckets, uint32_t *head,
                                                         uint32_t *tail, const uint32_t *redo,
                                                         const uint32_t *nredo) {
@@ -1198,7 +1019,6 @@ __global__ __launch_bounds__(64) void k_accumulate_redo(const uint32_t *pts29, c
         store_f29(d + 42, from_fq32(p.zzz));
     };
     const uint32_t cnt = *nredo;
-    S = acc_seg(offs, U, nthr, S);
     for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < cnt; r += gridDim.x * blockDim.x)
         segment32(redo[r], ld, st, sorted, offs, 1, U, S);
 }
@@ -1207,17 +1027,13 @@ __global__ __launch_bounds__(64) void k_accumulate_redo(const uint32_t *pts29, c
 // level k -> k+1: xyzz[i] = 2^c * (x, y)_i.  The c doublings run in radix
 // 2^29 (ec29.cuh xdbl29, as the reduction tree's; the points of the prime-order
 // group have Y != 0) between one conversion in and one out: the same canonical
-// XYZZ as the 32-bit chain (PNP_TABLE_DBL29=0), 25.6 instead of 28.9 ms per
+// XYZZ as a 32-bit chain, 25.6 instead of 28.9 ms per
 // level of 2^22 points (profiles/r04_kernel_stats_table_dbl29.csv) — part of
 // the first proof after a key or SRS change.
-#ifndef PNP_TABLE_DBL29
-#define PNP_TABLE_DBL29 1
-#endif
 __global__ __launch_bounds__(256) void k_table_dbl(const uint64_t *src, uint64_t n, int c,
                                                    uint64_t *xyzz) {
     uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
-#if PNP_TABLE_DBL29
     Xyzz29 q;
     q.x = from_fq32(load_fq(src + 12 * i));
     q.y = from_fq32(load_fq(src + 12 * i + 6));
@@ -1225,12 +1041,6 @@ __global__ __launch_bounds__(256) void k_table_dbl(const uint64_t *src, uint64_t
 #pragma unroll 1
     for (int k = 0; k < c; k++) q = xdbl29(q);
     store_xyzz(xyzz + 24 * i, to32(q));
-#else
-    Xyzz q = dbl_affine(load_fq(src + 12 * i), load_fq(src + 12 * i + 6));
-#pragma unroll 1
-    for (int k = 1; k < c; k++) q = dbl(q);
-    store_xyzz(xyzz + 24 * i, q);
-#endif
 }
 // XYZZ -> affine for CH consecutive points per lane, one Fermat inversion per
 // lane (Montgomery's trick over ZZZ; 1/ZZ = (ZZ/ZZZ)^2).  Points of the prime
@@ -1414,13 +1224,7 @@ static uint32_t acc_segment(uint64_t nent, bool folded) {
         slots = (uint64_t)cus * 4 * PNP_ACC_WAVES * 64;
     }
     const uint64_t per = (nent + slots - 1) / slots;  // entries per lane in one round
-    // PNP_ACC_ROUNDS=R: at most R rounds (longer segments, fewer split buckets
-    // to merge; experiments)
-    static const uint64_t max_rounds = [] {
-        const char *e = getenv("PNP_ACC_ROUNDS");
-        return e && atoi(e) > 0 ? (uint64_t)atoi(e) : ~0ULL;
-    }();
-    const uint64_t rounds = std::min(max_rounds, std::max<uint64_t>(1, per / S));
+    const uint64_t rounds = std::max<uint64_t>(1, per / S);
     // a batch smaller than one round at S = 64 (one MSM of a 2^19-point rank
     // range: ~35 entries per lane) takes shorter segments and fills the chip
     // instead of leaving part of it idle (more bucket pieces to merge, a few %
@@ -1461,13 +1265,13 @@ static void accumulate_group(MsmWork &wk, MsmGroup &gb, const GroupPlan &gp, con
         PNP_HIP(hipMemsetAsync(nredo, 0, 4, s));
         const uint32_t *t29 = reinterpret_cast<const uint32_t *>(table);
         const uint32_t blocks = (uint32_t)((nthr + 255) / 256);
-        hipLaunchKernelGGL(k_accumulate29, dim3(blocks), dim3(256), 0, s, t29, sorted, bstart, WB, nthr, S, bk29,
+        hipLaunchKernelGGL(k_accumulate29, dim3(blocks), dim3(256), 0, s, t29, sorted, bstart, WB, S, bk29,
                            head, tail, tailb, redo, nredo, tlist);
         PNP_HIP(hipGetLastError());
         // equal / opposite points or infinity inside a piece: exact recomputation
         // of the flagged lanes (the count stays on the device: no host sync)
         hipLaunchKernelGGL(k_accumulate_redo, dim3((uint32_t)std::min<uint64_t>((nthr + 63) / 64, 1024)), dim3(64), 0, s, t29,
-                           sorted, bstart, WB, nthr, S, bk29, head, tail, redo, nredo);
+                           sorted, bstart, WB, S, bk29, head, tail, redo, nredo);
         PNP_HIP(hipGetLastError());
         // split buckets into bk29 (in place, F29; empty ones stay unwritten), reduced by msm_reduce29
         need(gb.exc, 16);
@@ -1495,7 +1299,7 @@ static void accumulate_group(MsmWork &wk, MsmGroup &gb, const GroupPlan &gp, con
         if (table) {  // the real work, counted on the device (k_count_pieces)
             need(gb.wctr, 8 * (1 + WCTR_SLOTS));
             PNP_HIP(hipMemsetAsync(gb.wctr.p, 0, 8 * (1 + WCTR_SLOTS), s));
-            hipLaunchKernelGGL(k_count_pieces, dim3((uint32_t)((WB + 1023) / 1024)), dim3(1024), 0, s, bstart, WB, nthr, S,
+            hipLaunchKernelGGL(k_count_pieces, dim3((uint32_t)((WB + 1023) / 1024)), dim3(1024), 0, s, bstart, WB, S,
                                static_cast<unsigned long long *>(gb.wctr.p));
             PNP_HIP(hipGetLastError());
             gb.wctr_live = true;
@@ -1537,35 +1341,20 @@ static const uint64_t *reduce_group_exact(MsmGroup &gb, const GroupPlan &gp, con
     uint64_t *bk = gb.buckets.u64();
     const uint32_t *bk29 = static_cast<const uint32_t *>(gb.seg.p);
     const uint32_t *head = bk29 + 56 * WB, *tail = head + 56 * gb.nthr;
-    msm_merge_pieces29_exact(static_cast<const uint32_t *>(gb.offsets.p), WB, gb.S, gb.nthr, gb.pieces, bk29, head, tail,
+    msm_merge_pieces29_exact(static_cast<const uint32_t *>(gb.offsets.p), WB, gb.S, gb.pieces, bk29, head, tail,
                              bk, s);
     return msm_reduce(bk, (uint64_t)gp.nv, g.NB, bk + WB * 24, s);
-}
-
-static hipEvent_t ev_get(MsmWork &wk, int i) {
-    if (!wk.ev[i]) PNP_HIP(hipEventCreateWithFlags(&wk.ev[i], hipEventDisableTiming));
-    return wk.ev[i];
 }
 
 // B independent MSMs over the same n points, on this GPU only; the B results
 // (XYZZ) land in h_xyzz.  Per-window layout: the B*W windows are "virtual
 // windows" of NB buckets each.  Folded layout (table != nullptr): virtual
 // window b = MSM b with the W key rows of its windows, one bucket set.
-// Optionally (PNP_MSM_PIPE) the batch is split into two groups (halves of the
-// MSMs, or of the windows when B = 1) pipelined over two streams: group 1's
-// sort beside group 0's accumulation, group 0's bucket tree beside group 1's.
+// One group on one stream: the sort cannot be hidden under the accumulation
+// on this chip (the two-stream pipeline).
 // n_table / id_base: a folded table built over n_table points of which this
 // call's points are [id_base, id_base + n) (bucket-range mode keeps the full
 // table; a point-range batch then indexes into it); 0 = the table is this range
-static int pipe_min_b() {
-    static const int v = [] {
-        const char *e = getenv("PNP_MSM_PIPE");
-        return e ? std::max(1, atoi(e)) : 0;
-    }();
-    return v;
-}
-static bool pipe_off() { return pipe_min_b() == 0; }
-
 static void msm_local_batch(MsmWork &wk, const uint64_t *d_points, const uint64_t *const *d_scalars,
                             int B, uint64_t n, uint64_t *h_xyzz, hipStream_t s,
                             const uint64_t *table, uint64_t n_table = 0, uint64_t id_base = 0,
@@ -1580,14 +1369,8 @@ static void msm_local_batch(MsmWork &wk, const uint64_t *d_points, const uint64_
     auto need = [](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
     need(wk.digits, (uint64_t)g.W * B * n * 4);
     uint32_t *keys = static_cast<uint32_t *>(wk.digits.p);
-    // PNP_MSM_FUSE_DIGITS=0: separate digit and histogram passes (A/B)
-    static const bool fuse_env = [] {
-        const char *e = getenv("PNP_MSM_FUSE_DIGITS");
-        return !e || atoi(e) != 0;
-    }();
-    const bool no_pipe = pipe_off() || B < pipe_min_b();
-    // the fused pass makes the keys of the single standard folded group
-    const bool fuse = fuse_env && folded && B <= ScalarPtrs::MAX && no_pipe;
+    // the fused pass makes the keys of the standard folded group
+    const bool fuse = folded && B <= ScalarPtrs::MAX;
     if (!fuse) {
         for (int b = 0; b < B; b++) {
             hipLaunchKernelGGL(k_digits, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d_scalars[b], n,
@@ -1595,109 +1378,52 @@ static void msm_local_batch(MsmWork &wk, const uint64_t *d_points, const uint64_
             PNP_HIP(hipGetLastError());
         }
     }
-    // groups: (plan, first MSM of its results)
-    GroupPlan gp[2];
-    int ng = 1, first[2] = {0, 0};
-    KeyRows kr;
-    kr.n = n;
-    // Two-stream pipelining measured 3% SLOWER per proof on MI355X (the sort
-    // and tree kernels steal issue slots from the VALU-bound accumulation and
-    // slow down themselves): one group unless PNP_MSM_PIPE=1 (experiments).
-    // PNP_MSM_PIPE=B: pipeline batches of at least B MSMs only (experiments)
+    GroupPlan gp;
+    gp.kr.n = n;
     if (!folded) {
-        kr.vstride = 1, kr.off = 0, kr.rows = 1, kr.id_row0 = 0, kr.id_mul = 0;
-        gp[0] = {kr, B * g.W};
-    } else if (no_pipe) {
-        kr.vstride = g.W, kr.off = 0, kr.rows = g.W, kr.id_row0 = 0, kr.id_mul = n_table;
-        kr.id_base = id_base;
-        gp[0] = {kr, B};
-    } else if (B >= 2) {
-        const int h = (B + 1) / 2;
-        kr.vstride = g.W, kr.off = 0, kr.rows = g.W, kr.id_row0 = 0, kr.id_mul = n_table, kr.id_base = id_base;
-        gp[0] = {kr, h};
-        kr.off = h * g.W;
-        gp[1] = {kr, B - h};
-        first[1] = h;
-        ng = 2;
-    } else if (g.W >= 2) {  // one MSM: split its windows
-        const int h = g.W / 2;
-        kr.vstride = g.W, kr.off = 0, kr.rows = h, kr.id_row0 = 0, kr.id_mul = n_table, kr.id_base = id_base;
-        gp[0] = {kr, 1};
-        kr.off = h, kr.rows = g.W - h, kr.id_row0 = h;
-        gp[1] = {kr, 1};
-        ng = 2;
+        gp.kr.vstride = 1, gp.kr.off = 0, gp.kr.rows = 1, gp.kr.id_row0 = 0, gp.kr.id_mul = 0;
+        gp.nv = B * g.W;
     } else {
-        kr.vstride = g.W, kr.off = 0, kr.rows = g.W, kr.id_row0 = 0, kr.id_mul = n_table, kr.id_base = id_base;
-        gp[0] = {kr, 1};
+        gp.kr.vstride = g.W, gp.kr.off = 0, gp.kr.rows = g.W, gp.kr.id_row0 = 0, gp.kr.id_mul = n_table;
+        gp.kr.id_base = id_base;
+        gp.nv = B;
     }
-    if (seg_off) {  // MSM first[k] + v of group k starts at seg_off[first[k] + v] (window split: MSM 0)
-        for (int k = 0; k < ng; k++) {
-            gp[k].kr.nseg = gp[k].nv;
-            for (int v = 0; v < gp[k].nv; v++) gp[k].kr.seg_off[v] = seg_off[B == 1 ? 0 : first[k] + v];
-        }
+    if (seg_off) {  // MSM v starts at seg_off[v]
+        gp.kr.nseg = gp.nv;
+        for (int v = 0; v < gp.nv; v++) gp.kr.seg_off[v] = seg_off[v];
     }
     const uint64_t *pts = folded ? table : d_points;
-    const uint64_t *res[2] = {nullptr, nullptr};
-    if (ng == 1) {
-        sort_group(wk, wk.grp[0], keys, gp[0], g, s, fuse ? d_scalars : nullptr);
-        accumulate_group(wk, wk.grp[0], gp[0], g, pts, table, s);
-        res[0] = reduce_group(wk.grp[0], gp[0], g, s, folded);
-    } else {
-        if (!wk.s2) PNP_HIP(hipStreamCreateWithFlags(&wk.s2, hipStreamNonBlocking));
-        hipEvent_t evD = ev_get(wk, 0), evS1 = ev_get(wk, 1), evA0 = ev_get(wk, 2), evR0 = ev_get(wk, 3);
-        PNP_HIP(hipEventRecord(evD, s));
-        PNP_HIP(hipStreamWaitEvent(wk.s2, evD, 0));
-        sort_group(wk, wk.grp[1], keys, gp[1], g, wk.s2);
-        PNP_HIP(hipEventRecord(evS1, wk.s2));
-        sort_group(wk, wk.grp[0], keys, gp[0], g, s);
-        accumulate_group(wk, wk.grp[0], gp[0], g, pts, table, s);
-        PNP_HIP(hipEventRecord(evA0, s));
-        PNP_HIP(hipStreamWaitEvent(wk.s2, evA0, 0));
-        res[0] = reduce_group(wk.grp[0], gp[0], g, wk.s2, folded);
-        PNP_HIP(hipEventRecord(evR0, wk.s2));
-        PNP_HIP(hipStreamWaitEvent(s, evS1, 0));
-        accumulate_group(wk, wk.grp[1], gp[1], g, pts, table, s);
-        res[1] = reduce_group(wk.grp[1], gp[1], g, s, folded);
-        PNP_HIP(hipStreamWaitEvent(s, evR0, 0));
-    }
-    std::vector<uint64_t> win[2];
-    uint32_t exc[2] = {0, 0}, nredo[2] = {0, 0};
-    for (int k = 0; k < ng; k++) {
-        win[k].resize((size_t)gp[k].nv * 24);
-        PNP_HIP(hipMemcpyAsync(win[k].data(), res[k], win[k].size() * 8, hipMemcpyDeviceToHost, s));
-        if (folded) {
-            PNP_HIP(hipMemcpyAsync(&exc[k], wk.grp[k].exc.p, 4, hipMemcpyDeviceToHost, s));
-            PNP_HIP(hipMemcpyAsync(&nredo[k], wk.grp[k].redo.p, 4, hipMemcpyDeviceToHost, s));
-            wctr_fetch(wk.grp[k], s);
-        }
+    MsmGroup &gb = wk.grp;
+    sort_group(wk, gb, keys, gp, g, s, fuse ? d_scalars : nullptr);
+    accumulate_group(wk, gb, gp, g, pts, table, s);
+    const uint64_t *res = reduce_group(gb, gp, g, s, folded);
+    std::vector<uint64_t> win((size_t)gp.nv * 24);
+    uint32_t exc = 0, nredo = 0;
+    PNP_HIP(hipMemcpyAsync(win.data(), res, win.size() * 8, hipMemcpyDeviceToHost, s));
+    if (folded) {
+        PNP_HIP(hipMemcpyAsync(&exc, gb.exc.p, 4, hipMemcpyDeviceToHost, s));
+        PNP_HIP(hipMemcpyAsync(&nredo, gb.redo.p, 4, hipMemcpyDeviceToHost, s));
+        wctr_fetch(gb, s);
     }
     PNP_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < ng; k++) wctr_credit(wk, wk.grp[k]);
+    wctr_credit(wk, gb);
     // accumulation lanes recomputed exactly (a degenerate step in a piece)
-    if (wk.timer) wk.timer->credit("msm_redo_lanes", (double)nredo[0] + nredo[1]);
-    for (int k = 0; k < ng; k++) {
-        if (!exc[k]) continue;
+    if (wk.timer) wk.timer->credit("msm_redo_lanes", (double)nredo);
+    if (exc) {
         if (wk.timer) wk.timer->credit("msm_exact_fallback", 1);
-        res[k] = reduce_group_exact(wk.grp[k], gp[k], g, s);
-        PNP_HIP(hipMemcpyAsync(win[k].data(), res[k], win[k].size() * 8, hipMemcpyDeviceToHost, s));
+        res = reduce_group_exact(gb, gp, g, s);
+        PNP_HIP(hipMemcpyAsync(win.data(), res, win.size() * 8, hipMemcpyDeviceToHost, s));
         PNP_HIP(hipStreamSynchronize(s));
     }
     if (wk.timer) wk.timer->collect();
-    for (int b = 0; b < B; b++) put_xyzz(Xyzz::inf(), h_xyzz + 24 * b);
-    for (int k = 0; k < ng; k++) {
-        for (int v = 0; v < gp[k].nv; v++) {
-            if (folded) {
-                const int b = B == 1 ? 0 : first[k] + v;
-                put_xyzz(add(get_xyzz(h_xyzz + 24 * b), get_xyzz(&win[k][(size_t)v * 24])), h_xyzz + 24 * b);
-            }
-        }
-    }
-    if (!folded) {
+    if (folded) {  // virtual window b is MSM b
+        std::copy(win.begin(), win.end(), h_xyzz);
+    } else {
         for (int b = 0; b < B; b++) {
             Xyzz acc = Xyzz::inf();
             for (int w = g.W - 1; w >= 0; w--) {
                 for (int k = 0; k < g.c; k++) acc = dbl(acc);
-                acc = add(acc, get_xyzz(&win[0][((size_t)b * g.W + w) * 24]));
+                acc = add(acc, get_xyzz(&win[((size_t)b * g.W + w) * 24]));
             }
             put_xyzz(acc, h_xyzz + 24 * b);
         }
@@ -1793,7 +1519,7 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
     const uint64_t NBloc = (uint64_t)g.NB / W, n = p1 - p0;
     if (NBloc < 32) return false;
     auto need = [](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
-    MsmGroup &gb = wk.grp[0];
+    MsmGroup &gb = wk.grp;
     // 1. digits of this rank's points
     need(wk.digits, (uint64_t)g.W * B * std::max<uint64_t>(n, 1) * 4);
     uint32_t *keys = static_cast<uint32_t *>(wk.digits.p);
@@ -2104,11 +1830,10 @@ uint64_t msm_work_bytes(uint64_t n_pts, uint64_t n_cfg, int fold_c, int B, uint6
     return digits + counts + sort + acc;
 }
 uint64_t msm_work_held(const MsmWork &wk) {
-    uint64_t b = wk.digits.bytes + wk.part_counts.bytes + wk.rec_counts.bytes;
-    for (const MsmGroup &g : wk.grp)
-        b += g.counts.bytes + g.offsets.bytes + g.scan_tmp.bytes + g.ent.bytes + g.fkey.bytes + g.sorted.bytes +
-             g.buckets.bytes + g.seg.bytes + g.redo.bytes + g.exc.bytes + g.heavy.bytes + g.wctr.bytes;
-    return b;
+    const MsmGroup &g = wk.grp;
+    return wk.digits.bytes + wk.part_counts.bytes + wk.rec_counts.bytes + g.counts.bytes + g.offsets.bytes +
+           g.scan_tmp.bytes + g.ent.bytes + g.fkey.bytes + g.sorted.bytes + g.buckets.bytes + g.seg.bytes +
+           g.redo.bytes + g.exc.bytes + g.heavy.bytes + g.wctr.bytes;
 }
 
 void msm_point_range(uint64_t n, int rank, int world, uint64_t &p0, uint64_t &p1) {

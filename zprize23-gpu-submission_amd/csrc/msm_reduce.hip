@@ -147,13 +147,12 @@ constexpr uint32_t MERGE_HEAVY = PNP_MERGE_HEAVY;
 // One merge lane per listed tail (tlist: the accumulation lanes that left
 // one, compacted by k_accumulate29): a wave is 64 merges, where one lane per
 // accumulation lane ran ~1 in 3 of its lanes (a segment of ~3 buckets splits one)
-__global__ __launch_bounds__(256) void k_merge_tails29(const uint32_t *offs, uint64_t U, uint64_t nthr, uint32_t S,
+__global__ __launch_bounds__(256) void k_merge_tails29(const uint32_t *offs, uint64_t U, uint32_t S,
                                                        const uint32_t *tailb, const uint32_t *tlist, uint32_t *bk29,
                                                        const uint32_t *head, const uint32_t *tail, uint32_t *exc,
                                                        uint32_t *heavy, uint32_t *nheavy) {
     const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (q >= tlist[0]) return;
-    S = acc_seg(offs, U, nthr, S);
     const uint64_t t = tlist[1 + q];
     const uint32_t u = tailb[t];
     const uint32_t t1 = (offs[u + 1] - 1) / S;
@@ -170,12 +169,11 @@ __global__ __launch_bounds__(256) void k_merge_tails29(const uint32_t *offs, uin
 // the queued heavy buckets, one workgroup each (grid-stride over the queue):
 // 256 lanes sum every 256th piece, then an LDS tree of log2 of the lanes that
 // hold a piece (8 levels from 128 pieces on, 4 for a bucket of 16)
-__global__ __launch_bounds__(256) void k_merge_heavy29(const uint32_t *offs, uint64_t U, uint64_t nthr, uint32_t S,
+__global__ __launch_bounds__(256) void k_merge_heavy29(const uint32_t *offs, uint64_t U, uint32_t S,
                                                        uint32_t *bk29, const uint32_t *head, const uint32_t *tail,
                                                        uint32_t *exc, const uint32_t *heavy, const uint32_t *nheavy) {
     __shared__ uint32_t lds[256 * 56];
     const uint32_t cnt = *nheavy;
-    S = acc_seg(offs, U, nthr, S);
     uint32_t *mine = lds + 56 * threadIdx.x;
     for (uint32_t q = blockIdx.x; q < cnt; q += gridDim.x) {
         const uint32_t g = heavy[q];
@@ -206,11 +204,11 @@ void msm_merge_pieces29(const uint32_t *offs, uint64_t U, uint32_t S, uint64_t n
     PNP_HIP(hipMemsetAsync(nheavy, 0, 4, s));
     // (the count stays on the device: a grid for every accumulation lane, the
     // waves past the count exit at once)
-    hipLaunchKernelGGL(k_merge_tails29, dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, s, offs, U, nthr, S,
+    hipLaunchKernelGGL(k_merge_tails29, dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, s, offs, U, S,
                        tailb, tlist, bk29, head, tail, exc, list, nheavy);
     PNP_HIP(hipGetLastError());
     // a small grid: it exits at once when nothing was queued
-    hipLaunchKernelGGL(k_merge_heavy29, dim3(256), dim3(256), 0, s, offs, U, nthr, S, bk29, head, tail, exc, list,
+    hipLaunchKernelGGL(k_merge_heavy29, dim3(256), dim3(256), 0, s, offs, U, S, bk29, head, tail, exc, list,
                        nheavy);
     PNP_HIP(hipGetLastError());
 }
@@ -221,12 +219,11 @@ void msm_merge_pieces29(const uint32_t *offs, uint64_t U, uint32_t S, uint64_t n
 // (the F29 merge writes only split and empty buckets).  Writes bk (R384) for
 // the 32-bit msm_reduce.
 __device__ __forceinline__ Xyzz piece29(const uint32_t *p) { return to32(load_xyzz29(p)); }
-__global__ __launch_bounds__(256) void k_merge_pieces29_exact(const uint32_t *offs, uint64_t U, uint64_t nthr,
+__global__ __launch_bounds__(256) void k_merge_pieces29_exact(const uint32_t *offs, uint64_t U,
                                                               uint32_t S, int G, const uint32_t *bk29,
                                                               const uint32_t *head, const uint32_t *tail,
                                                               uint64_t *bk) {
     __shared__ uint64_t lds[256 * 24];
-    S = acc_seg(offs, U, nthr, S);
     const uint64_t g = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) / G;
     const int j = threadIdx.x % G;
     bool live = false;
@@ -257,13 +254,13 @@ __global__ __launch_bounds__(256) void k_merge_pieces29_exact(const uint32_t *of
     if (live && j == 0) store_xyzz(bk + 24 * g, acc);
 }
 
-void msm_merge_pieces29_exact(const uint32_t *offs, uint64_t U, uint32_t S, uint64_t nthr, uint32_t pieces,
+void msm_merge_pieces29_exact(const uint32_t *offs, uint64_t U, uint32_t S, uint32_t pieces,
                               const uint32_t *bk29, const uint32_t *head, const uint32_t *tail, uint64_t *bk,
                               hipStream_t s) {
     int G = 1;
     while (G < 8 && (uint32_t)G * 8 <= pieces) G *= 2;
     const uint64_t blocks = (U * G + 255) / 256;
-    hipLaunchKernelGGL(k_merge_pieces29_exact, dim3((uint32_t)blocks), dim3(256), 0, s, offs, U, nthr, S, G, bk29,
+    hipLaunchKernelGGL(k_merge_pieces29_exact, dim3((uint32_t)blocks), dim3(256), 0, s, offs, U, S, G, bk29,
                        head, tail, bk);
     PNP_HIP(hipGetLastError());
 }
@@ -500,10 +497,7 @@ const uint64_t *msm_reduce29(const uint32_t *bk29, const uint32_t *offs, uint64_
     // additions per bucket and a tree level 2, so narrower leaves and one more
     // level are shorter — rank 0 of 8 28.6 -> 28.2 ms, one GPU unaffected
     // (its 2^19-bucket windows keep 8; profiles/r06_ab_devseg_leaf.txt)
-#ifndef PNP_LEAF_SMALL4
-#define PNP_LEAF_SMALL4 1
-#endif
-    const int LW = NB >= 2 * PNP_LEAF_W ? (PNP_LEAF_SMALL4 && NB <= (1 << 16) && PNP_LEAF_W > 4 ? 4 : PNP_LEAF_W) : 2;
+    const int LW = NB >= 2 * PNP_LEAF_W ? (NB <= (1 << 16) && PNP_LEAF_W > 4 ? 4 : PNP_LEAF_W) : 2;
     if (NB < 2 * LW) {
         set_error("msm_reduce29: %d buckets per window", NB);
         throw Error(PNP_E_ARG);
@@ -513,12 +507,9 @@ const uint64_t *msm_reduce29(const uint32_t *bk29, const uint32_t *offs, uint64_
     uint64_t *roots = reinterpret_cast<uint64_t *>(scratch + 252 * m);
     const dim3 lgrid((uint32_t)((m + 255) / 256));
     // small leaf launches (the 8-rank ranges' one- and two-MSM batches) on quads
-    static const uint64_t leaf_wide = [] {
-        const char *e = getenv("PNP_LEAF_WIDE");
-        return (uint64_t)(e ? atoll(e) : 32768);
-    }();
+    constexpr uint64_t LEAF_WIDE_MAX = 32768;
     const dim3 wgrid((uint32_t)((4 * m + 255) / 256));
-    if (LW == 4 && m <= leaf_wide)
+    if (LW == 4 && m <= LEAF_WIDE_MAX)
         hipLaunchKernelGGL(k_tree_leafw29w<4>, wgrid, dim3(256), 0, s, bk29, offs, m, a, exc);
     else if (LW == 2)
         hipLaunchKernelGGL(k_tree_leafw29<2>, lgrid, dim3(256), 0, s, bk29, offs, m, a, exc);
@@ -527,14 +518,11 @@ const uint64_t *msm_reduce29(const uint32_t *bk29, const uint32_t *offs, uint64_
     else
         hipLaunchKernelGGL(k_tree_leafw29<PNP_LEAF_W>, lgrid, dim3(256), 0, s, bk29, offs, m, a, exc);
     PNP_HIP(hipGetLastError());
-    // levels of at most PNP_TREE_WIDE nodes (latency-bound) on quads
-    static const uint64_t wide_max = [] {
-        const char *e = getenv("PNP_TREE_WIDE");
-        return (uint64_t)(e ? atoll(e) : 16384);
-    }();
+    // levels of at most TREE_WIDE_MAX nodes (latency-bound) on quads
+    constexpr uint64_t TREE_WIDE_MAX = 16384;
     while (m > nwin) {
         m /= 2;
-        if (m <= wide_max)
+        if (m <= TREE_WIDE_MAX)
             hipLaunchKernelGGL(k_tree_level29w, dim3((uint32_t)((4 * m + 255) / 256), 3), dim3(256), 0, s, a, m, b,
                                exc);
         else

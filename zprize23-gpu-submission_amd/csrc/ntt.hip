@@ -14,11 +14,10 @@
 //     conflict-free.
 //   * Twiddles w_N^e come from a per-size table (computed once per context,
 //     HBM-resident; its hot part lives in L2/MALL).
-//   * The DIF output is bit-reversed; one in-place tiled pass (32x32 tiles,
+//   * The DIF output is bit-reversed; one in-place tiled pass (16x16 tiles,
 //     tile pairs swapped through LDS) restores natural order and fuses the
 //     N^-1 and g^-i scalings of the inverse / coset-inverse transforms.
 #include "pnp_internal.h"
-#include "fr29.cuh"
 
 namespace pnp {
 
@@ -124,38 +123,6 @@ static const uint64_t *ntt_twiddle_rows(NttTables &t, uint32_t lg, bool inverse,
     return p;
 }
 
-// a 2^256-form table (32-bit Montgomery Fr) -> its 2^261 form in radix 2^29
-__global__ void k_table_to_r29(const uint64_t *tab, uint64_t count, uint32_t *out) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(tab + 4 * i);
-    R29 c;
-#pragma unroll
-    for (int k = 0; k < 9; k++) c.l[k] = R29_C266[k];
-    const R29 x = r29_canon(r29_mul(r29_from_words(w), c));
-    uint32_t *o = out + 9 * i;
-#pragma unroll
-    for (int k = 0; k < 9; k++) o[k] = x.l[k];
-}
-
-static const uint32_t *to_r29_table(std::map<uint32_t, DevBuf> &m, uint32_t key, const uint64_t *tab,
-                                    uint64_t count, hipStream_t s) {
-    auto it = m.find(key);
-    if (it != m.end()) return static_cast<const uint32_t *>(it->second.p);
-    DevBuf buf(count * 36);
-    hipLaunchKernelGGL(k_table_to_r29, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, s, tab, count,
-                       static_cast<uint32_t *>(buf.p));
-    PNP_HIP(hipGetLastError());
-    const uint32_t *p = static_cast<const uint32_t *>(buf.p);
-    m.emplace(key, std::move(buf));
-    return p;
-}
-
-static const uint32_t *ntt_twiddles29(NttTables &t, uint32_t lg, bool inverse, hipStream_t s) {
-    const uint64_t half = lg ? (1ULL << (lg - 1)) : 1;
-    return to_r29_table(inverse ? t.inv29 : t.fwd29, lg, ntt_twiddles(t, lg, inverse, s), half, s);
-}
-
 void ntt_prepare_coset(NttTables &t, hipStream_t s) {
     if (t.coset_ready) return;
     Fr g = host_gen();
@@ -180,97 +147,11 @@ __device__ __forceinline__ Fr coset_pow(const uint64_t *hi, const uint64_t *lo, 
 // Optional fusions: `src` + `pre` (load src[idx & src_mask] * pre[idx] instead
 // of data[idx]: the coset twist of an LDE in its first pass) and `post` (store
 // x * post[idx]: the block twist after the last inverse pass).
-template <int K, bool DIT>
-__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(uint64_t *data, const uint64_t *tw,
-                                                           uint32_t lg_n, uint32_t lg_hlo,
-                                                           const uint64_t *src, const uint64_t *pre,
-                                                           uint64_t src_mask, const uint64_t *post) {
-    constexpr int G = TILE >> K;
-    __shared__ uint4 lds_lo[TILE];
-    __shared__ uint4 lds_hi[TILE];
-    const uint64_t hlo = 1ULL << lg_hlo;
-    const uint64_t gid0 = (uint64_t)blockIdx.x * G;
-    // load: element (m, g) of the tile -> lds[m*G + g]
-    for (int e = threadIdx.x; e < TILE; e += NTT_THREADS) {
-        int g = e % G, m = e / G;
-        uint64_t gid = gid0 + g;
-        uint64_t j = gid & (hlo - 1), b = gid >> lg_hlo;
-        uint64_t idx = (b << (lg_hlo + K)) + j + ((uint64_t)m << lg_hlo);
-        if (src) {
-            Fr x = load_fr(src, idx & src_mask);
-            if (pre) x = x * load_fr(pre, idx);
-            lds_lo[e] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-            lds_hi[e] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-        } else {
-            const uint4 *p = reinterpret_cast<const uint4 *>(data + 4 * idx);
-            lds_lo[e] = p[0];
-            lds_hi[e] = p[1];
-        }
-    }
-    __syncthreads();
-    for (int step = 0; step < K; step++) {
-        const int l = DIT ? step : K - 1 - step;
-        const uint32_t sh = lg_n - 1 - lg_hlo - l;
-        // half size 1: every twiddle is w^0 = 1 (uniform branch, no product)
-        const bool unit = lg_hlo == 0 && l == 0;
-        for (int bf = threadIdx.x; bf < TILE / 2; bf += NTT_THREADS) {
-            int g = bf % G, q = bf / G;
-            int mlow = q & ((1 << l) - 1);
-            int m = ((q >> l) << (l + 1)) | mlow;
-            int e0 = m * G + g, e1 = (m + (1 << l)) * G + g;
-            uint64_t gid = gid0 + g;
-            uint64_t j = gid & (hlo - 1);
-            uint64_t r = j + ((uint64_t)mlow << lg_hlo);
-            uint4 a0 = lds_lo[e0], a1 = lds_hi[e0], b0 = lds_lo[e1], b1 = lds_hi[e1];
-            Fr a, b;
-            a.v[0] = a0.x; a.v[1] = a0.y; a.v[2] = a0.z; a.v[3] = a0.w;
-            a.v[4] = a1.x; a.v[5] = a1.y; a.v[6] = a1.z; a.v[7] = a1.w;
-            b.v[0] = b0.x; b.v[1] = b0.y; b.v[2] = b0.z; b.v[3] = b0.w;
-            b.v[4] = b1.x; b.v[5] = b1.y; b.v[6] = b1.z; b.v[7] = b1.w;
-            Fr s, d;
-            if (unit) {
-                s = a + b;
-                d = a - b;
-            } else if (DIT) {
-                Fr t = b * load_fr(tw, r << sh);
-                s = a + t;
-                d = a - t;
-            } else {
-                s = a + b;
-                d = (a - b) * load_fr(tw, r << sh);
-            }
-            lds_lo[e0] = make_uint4(s.v[0], s.v[1], s.v[2], s.v[3]);
-            lds_hi[e0] = make_uint4(s.v[4], s.v[5], s.v[6], s.v[7]);
-            lds_lo[e1] = make_uint4(d.v[0], d.v[1], d.v[2], d.v[3]);
-            lds_hi[e1] = make_uint4(d.v[4], d.v[5], d.v[6], d.v[7]);
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < TILE; e += NTT_THREADS) {
-        int g = e % G, m = e / G;
-        uint64_t gid = gid0 + g;
-        uint64_t j = gid & (hlo - 1), b = gid >> lg_hlo;
-        uint64_t idx = (b << (lg_hlo + K)) + j + ((uint64_t)m << lg_hlo);
-        if (post) {
-            uint4 lo = lds_lo[e], hi = lds_hi[e];
-            Fr x;
-            x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w;
-            x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w;
-            store_fr(data, idx, x * load_fr(post, idx));
-        } else {
-            uint4 *dst = reinterpret_cast<uint4 *>(data + 4 * idx);
-            dst[0] = lds_lo[e];
-            dst[1] = lds_hi[e];
-        }
-    }
-}
-
-// The same pass with two levels per LDS round trip (radix-4 groups): each of
-// 256 lanes reads 4 elements, does the 4 butterflies of two consecutive
-// levels in registers (3 twiddles) and writes 4 elements back, so the tile
-// makes half the LDS round trips and barriers of k_ntt_pass; an odd K ends
-// (DIF) or ends (DIT) with one radix-2 level.  Same indexing and twiddles as
-// k_ntt_pass (level l, group element m: pair distance 2^l in m).
+// Two levels per LDS round trip (radix-4 groups): each of 256 lanes reads 4
+// elements, does the 4 butterflies of two consecutive levels in registers
+// (3 twiddles) and writes 4 elements back, so the tile makes one LDS round
+// trip and barrier per two levels; an odd K ends (DIF) or ends (DIT) with one
+// radix-2 level.  Level l pairs the group elements m at distance 2^l.
 #ifndef PNP_NTT4_THREADS
 #define PNP_NTT4_THREADS 256
 #endif
@@ -447,238 +328,6 @@ __global__ __launch_bounds__(NTT4_THREADS) void k_ntt_pass4(uint64_t *data, cons
     }
 }
 
-// The same pass in radix-2^29 arithmetic (fr29.cuh): canonical 2^256-form Fr
-// in and out (the HBM layout is unchanged), nine-limb values in LDS (two
-// 16-byte planes + one 4-byte plane, 36 KiB per tile), twiddles / twists from
-// the 2^261-form tables.  Bounds (tests/test_fr29.py): a DIF level l of the
-// pass doubles the inputs (< 2^l 1.04 r), its difference adds 2^(l+1) r; a DIT
-// level adds a product output (< 4 r) and 4 r; outputs < 2^264 -> r29_canon.
-template <int K, bool DIT>
-__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass29(uint64_t *data, const uint32_t *tw,
-                                                             uint32_t lg_n, uint32_t lg_hlo,
-                                                             const uint64_t *src, const uint32_t *pre,
-                                                             uint64_t src_mask, const uint32_t *post) {
-    constexpr int G = TILE >> K;
-    __shared__ uint4 l_lo[TILE];
-    __shared__ uint4 l_mid[TILE];
-    __shared__ uint32_t l_top[TILE];
-    auto put = [&](int e, const R29 &x) {
-        l_lo[e] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]);
-        l_mid[e] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]);
-        l_top[e] = x.l[8];
-    };
-    auto get = [&](int e) {
-        const uint4 a = l_lo[e], b = l_mid[e];
-        R29 x;
-        x.l[0] = a.x; x.l[1] = a.y; x.l[2] = a.z; x.l[3] = a.w;
-        x.l[4] = b.x; x.l[5] = b.y; x.l[6] = b.z; x.l[7] = b.w;
-        x.l[8] = l_top[e];
-        return x;
-    };
-    const uint64_t hlo = 1ULL << lg_hlo;
-    const uint64_t gid0 = (uint64_t)blockIdx.x * G;
-    for (int e = threadIdx.x; e < TILE; e += NTT_THREADS) {
-        const int g = e % G, m = e / G;
-        const uint64_t gid = gid0 + g;
-        const uint64_t j = gid & (hlo - 1), b = gid >> lg_hlo;
-        const uint64_t idx = (b << (lg_hlo + K)) + j + ((uint64_t)m << lg_hlo);
-        const uint4 *p = reinterpret_cast<const uint4 *>((src ? src + 4 * (idx & src_mask) : data + 4 * idx));
-        const uint4 q0 = p[0], q1 = p[1];
-        const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        R29 x = r29_from_words(w);
-        if (src) x = r29_mul(x, r29_load(pre, idx));
-        put(e, x);
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int step = 0; step < K; step++) {
-        const int l = DIT ? step : K - 1 - step;
-        const uint32_t sh = lg_n - 1 - lg_hlo - l;
-        const bool unit = lg_hlo == 0 && l == 0;  // half size 1: twiddle 1, no product
-        const uint32_t *kd = R29_KDIF[step];
-        for (int bf = threadIdx.x; bf < TILE / 2; bf += NTT_THREADS) {
-            const int g = bf % G, q = bf / G;
-            const int mlow = q & ((1 << l) - 1);
-            const int m = ((q >> l) << (l + 1)) | mlow;
-            const int e0 = m * G + g, e1 = (m + (1 << l)) * G + g;
-            const uint64_t j = (gid0 + g) & (hlo - 1);
-            const uint64_t r = j + ((uint64_t)mlow << lg_hlo);
-            const R29 a = get(e0), b = get(e1);
-            R29 s, d;
-            if (DIT) {
-                const R29 t = unit ? b : r29_mul(b, r29_load(tw, r << sh));
-                s = r29_add(a, t);
-                d = r29_sub(a, t, R29_KDIT);
-            } else {
-                s = r29_add(a, b);
-                d = r29_sub(a, b, kd);
-                if (!unit) d = r29_mul(d, r29_load(tw, r << sh));
-            }
-            put(e0, s);
-            put(e1, d);
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < TILE; e += NTT_THREADS) {
-        const int g = e % G, m = e / G;
-        const uint64_t gid = gid0 + g;
-        const uint64_t j = gid & (hlo - 1), b = gid >> lg_hlo;
-        const uint64_t idx = (b << (lg_hlo + K)) + j + ((uint64_t)m << lg_hlo);
-        R29 x = get(e);
-        if (post) x = r29_mul(x, r29_load(post, idx));
-        x = r29_canon(x);
-        uint32_t w[8];
-        r29_to_words(x, w);
-        uint4 *dst = reinterpret_cast<uint4 *>(data + 4 * idx);
-        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
-}
-
-// The radix-2^29 pass with two levels per LDS round trip (radix-4 groups as
-// k_ntt_pass4, arithmetic as k_ntt_pass29).  Every element meets exactly the
-// operations of k_ntt_pass29 in the same order — level by level, the same
-// lifted constant R29_KDIF[step] for the differences of step `step`, the same
-// twiddle products — so the bounds tests/test_fr29.py asserts for that pass
-// hold here unchanged.  Per butterfly the radix-2^29 product (153 bare
-// multiply-adds, no carry instructions, no hazard s_nops) issues ~20% fewer
-// VALU cycles than the 32-bit one (256 multiply-adds and carries); the radix-4
-// grouping halves the LDS round trips of the nine-limb planes.
-template <int K, bool DIT>
-__global__ __launch_bounds__(NTT4_THREADS) void k_ntt_pass4_29(uint64_t *data, const uint32_t *tw,
-                                                                uint32_t lg_n, uint32_t lg_hlo,
-                                                                const uint64_t *src, const uint32_t *pre,
-                                                                uint64_t src_mask, const uint32_t *post) {
-    constexpr int G = TILE >> K;
-    __shared__ uint4 l_lo[TILE];
-    __shared__ uint4 l_mid[TILE];
-    __shared__ uint32_t l_top[TILE];
-    auto put = [&](int e, const R29 &x) {
-        l_lo[e] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]);
-        l_mid[e] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]);
-        l_top[e] = x.l[8];
-    };
-    auto get = [&](int e) {
-        const uint4 a = l_lo[e], b = l_mid[e];
-        R29 x;
-        x.l[0] = a.x; x.l[1] = a.y; x.l[2] = a.z; x.l[3] = a.w;
-        x.l[4] = b.x; x.l[5] = b.y; x.l[6] = b.z; x.l[7] = b.w;
-        x.l[8] = l_top[e];
-        return x;
-    };
-    const uint64_t hlo = 1ULL << lg_hlo;
-    const uint64_t gid0 = (uint64_t)blockIdx.x * G;
-    for (int e = threadIdx.x; e < TILE; e += NTT4_THREADS) {
-        const int g = e % G, m = e / G;
-        const uint64_t gid = gid0 + g;
-        const uint64_t j = gid & (hlo - 1), b = gid >> lg_hlo;
-        const uint64_t idx = (b << (lg_hlo + K)) + j + ((uint64_t)m << lg_hlo);
-        const uint4 *p = reinterpret_cast<const uint4 *>((src ? src + 4 * (idx & src_mask) : data + 4 * idx));
-        const uint4 q0 = p[0], q1 = p[1];
-        const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        R29 x = r29_from_words(w);
-        if (src && pre) x = r29_mul(x, r29_load(pre, idx));
-        put(e, x);
-    }
-    __syncthreads();
-    auto twl = [&](uint64_t j, int l, uint32_t mlow) {
-        return r29_load(tw, (j + ((uint64_t)mlow << lg_hlo)) << (lg_n - 1 - lg_hlo - l));
-    };
-    constexpr int NPAIR = K / 2;
-#pragma unroll 1
-    for (int pr = 0; pr < NPAIR; pr++) {
-        // DIF: levels (hi, hi - 1) from K - 1 down; DIT: (lo, lo + 1) from 0 up
-        const int l = DIT ? 2 * pr : K - 1 - 2 * pr;
-        const int lb = DIT ? l : l - 1;
-        const int step = 2 * pr;  // the pass's step of the pair's first level (k_ntt_pass29 numbering)
-        for (int q = threadIdx.x; q < TILE / 4; q += NTT4_THREADS) {
-            const int g = q % G, q4 = q / G;
-            const uint32_t ml = q4 & ((1 << lb) - 1);
-            const int m = ((q4 >> lb) << (lb + 2)) | (int)ml;
-            const int e0 = m * G + g, e1 = (m + (1 << lb)) * G + g, e2 = (m + (2 << lb)) * G + g,
-                      e3 = (m + (3 << lb)) * G + g;
-            const uint64_t j = (gid0 + g) & (hlo - 1);
-            R29 x0 = get(e0), x1 = get(e1), x2 = get(e2), x3 = get(e3);
-            const bool unit = lg_hlo == 0 && lb == 0;  // level lb has half size 1
-            if (DIT) {
-                // level lb (step): (x0, x1), (x2, x3), one twiddle
-                R29 t0 = x1, t1 = x3;
-                if (!unit) {
-                    const R29 w = twl(j, lb, ml);
-                    t0 = r29_mul(x1, w);
-                    t1 = r29_mul(x3, w);
-                }
-                x1 = r29_sub(x0, t0, R29_KDIT); x0 = r29_add(x0, t0);
-                x3 = r29_sub(x2, t1, R29_KDIT); x2 = r29_add(x2, t1);
-                // level lb + 1 (step + 1): (x0, x2) low bits ml, (x1, x3) ml + 2^lb
-                R29 t = r29_mul(x2, twl(j, lb + 1, ml));
-                x2 = r29_sub(x0, t, R29_KDIT); x0 = r29_add(x0, t);
-                t = r29_mul(x3, twl(j, lb + 1, ml + (1u << lb)));
-                x3 = r29_sub(x1, t, R29_KDIT); x1 = r29_add(x1, t);
-            } else {
-                // level lb + 1 (step): (x0, x2) low bits ml, (x1, x3) ml + 2^lb
-                const uint32_t *k0 = R29_KDIF[step], *k1 = R29_KDIF[step + 1];
-                R29 d = r29_mul(r29_sub(x0, x2, k0), twl(j, lb + 1, ml)); x0 = r29_add(x0, x2); x2 = d;
-                d = r29_mul(r29_sub(x1, x3, k0), twl(j, lb + 1, ml + (1u << lb))); x1 = r29_add(x1, x3); x3 = d;
-                // level lb (step + 1): (x0, x1), (x2, x3)
-                if (unit) {
-                    d = r29_sub(x0, x1, k1); x0 = r29_add(x0, x1); x1 = d;
-                    d = r29_sub(x2, x3, k1); x2 = r29_add(x2, x3); x3 = d;
-                } else {
-                    const R29 w = twl(j, lb, ml);
-                    d = r29_mul(r29_sub(x0, x1, k1), w); x0 = r29_add(x0, x1); x1 = d;
-                    d = r29_mul(r29_sub(x2, x3, k1), w); x2 = r29_add(x2, x3); x3 = d;
-                }
-            }
-            put(e0, x0);
-            put(e1, x1);
-            put(e2, x2);
-            put(e3, x3);
-        }
-        __syncthreads();
-    }
-    if (K & 1) {  // the remaining level: DIF level 0 (step K - 1), DIT level K - 1
-        const int l = DIT ? K - 1 : 0;
-        const bool unit = lg_hlo == 0 && l == 0;
-        const uint32_t *kd = R29_KDIF[K - 1];
-        for (int bf = threadIdx.x; bf < TILE / 2; bf += NTT4_THREADS) {
-            const int g = bf % G, q = bf / G;
-            const int mlow = q & ((1 << l) - 1);
-            const int m = ((q >> l) << (l + 1)) | mlow;
-            const int e0 = m * G + g, e1 = (m + (1 << l)) * G + g;
-            const uint64_t j = (gid0 + g) & (hlo - 1);
-            const R29 a = get(e0), b = get(e1);
-            R29 s2, d;
-            if (DIT) {
-                const R29 t = unit ? b : r29_mul(b, twl(j, l, (uint32_t)mlow));
-                s2 = r29_add(a, t);
-                d = r29_sub(a, t, R29_KDIT);
-            } else {
-                s2 = r29_add(a, b);
-                d = r29_sub(a, b, kd);
-                if (!unit) d = r29_mul(d, twl(j, l, (uint32_t)mlow));
-            }
-            put(e0, s2);
-            put(e1, d);
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < TILE; e += NTT4_THREADS) {
-        const int g = e % G, m = e / G;
-        const uint64_t gid = gid0 + g;
-        const uint64_t j = gid & (hlo - 1), b = gid >> lg_hlo;
-        const uint64_t idx = (b << (lg_hlo + K)) + j + ((uint64_t)m << lg_hlo);
-        R29 x = get(e);
-        if (post) x = r29_mul(x, r29_load(post, idx));
-        x = r29_canon(x);
-        uint32_t w[8];
-        r29_to_words(x, w);
-        uint4 *dst = reinterpret_cast<uint4 *>(data + 4 * idx);
-        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
-}
-
 // small transforms (N < TILE): one workgroup does everything in LDS
 template <bool DIT>
 __global__ __launch_bounds__(NTT_THREADS) void k_ntt_small(uint64_t *data, const uint64_t *tw,
@@ -747,10 +396,9 @@ __device__ __forceinline__ Fr apply_scale(const Scale &s, Fr x, uint64_t i) {
 }
 
 // lg >= 2 TB: index = hi | mid | lo (TB bits each end); tile(mid) <->
-// tile(rev(mid)) transposed.  TB = 4 (default): 16 x 16 tiles, 17 KB of LDS
-// per workgroup, one element per lane per tile; TB = 5 (32 x 32, 68 KB: two
-// workgroups per CU) moved 256 MB in ~0.3 ms at 2^22, ~0.9 TB/s.  Rows of a
-// tile are 2^TB consecutive elements (512 B at TB = 4: four whole lines).
+// tile(rev(mid)) transposed.  TB = 4: 16 x 16 tiles, 17 KB of LDS per
+// workgroup, one element per lane per tile.  Rows of a tile are 2^TB
+// consecutive elements (512 B at TB = 4: four whole lines).
 template <int TB>
 __global__ __launch_bounds__(256) void k_bitrev_tiles(uint64_t *data, uint32_t lg, Scale sc) {
     constexpr int T = 1 << TB, TP = T + 1;
@@ -836,35 +484,12 @@ __global__ void k_pad_coset(const uint64_t *in, uint64_t *out, uint64_t n, uint6
     store_fr(out, i, x);
 }
 
-// Fused extras of the first (src, pre) and last (post) pass, see k_ntt_pass
+// Fused extras of the first (src, pre) and last (post) pass, see k_ntt_pass4
 struct PassFuse {
     const uint64_t *src = nullptr, *pre = nullptr, *post = nullptr;
     uint64_t src_mask = 0;
-    const uint32_t *pre29 = nullptr, *post29 = nullptr;  // the 2^261 forms of pre / post
 };
 
-// PNP_NTT_R4=0: the radix-2 passes (k_ntt_pass) instead of k_ntt_pass4
-static bool ntt4_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PNP_NTT_R4");
-        return !(e && atoi(e) == 0);
-    }();
-    return on;
-}
-
-// PNP_NTT29=1: the radix-2^29 passes (k_ntt_pass29).  Measured SLOWER than the
-// 32-bit-limb passes on MI355X (same-box, n = 2^22: 12.9 vs 11.6 ms for the
-// <7, DIF> passes of a proof): the v_addc_co_u32 of the 32-bit product issues
-// at the full VALU rate inside the multiply-add chain, so the 29-bit product
-// saves fewer cycles than its 36-byte LDS planes (4 instead of 5 workgroups
-// per CU), extra LDS instructions and per-pass canonicalisation cost.
-static bool ntt29_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PNP_NTT29");
-        return e && atoi(e) != 0;
-    }();
-    return on;
-}
 __global__ void k_mul_table(uint64_t *d, const uint64_t *T, uint64_t N);
 __global__ void k_lde_twist(const uint64_t *in, const uint64_t *T, uint64_t *out, uint64_t n, uint64_t N);
 
@@ -907,62 +532,18 @@ static void ntt_core(NttTables &t, uint64_t *d, uint32_t lg, bool inverse, bool 
         rem -= ks[p];
     }
     uint32_t lo = dit ? 0 : lg;  // DIF: current top exponent; DIT: current bottom
-    // radix 2^29 (PNP_NTT29): every pass of at most 8 levels (R29_KDIF's
-    // steps), with the 2^261-form twists where a pass fuses one
-    bool r29 = ntt29_enabled() && (!fz.pre || fz.pre29) && (!fz.post || fz.post29);
-    for (int p = 0; p < npass; p++) r29 &= ks[p] <= 8;
-    const uint32_t *tw29 = r29 ? ntt_twiddles29(t, lg, inverse, s) : nullptr;
     for (int p = 0; p < npass; p++) {
         const int k = ks[p];
         const uint32_t lg_hlo = dit ? lo : lo - k;
         const uint32_t blocks = (uint32_t)((N >> k) / (TILE >> k));
         const uint64_t *src = p == 0 ? fz.src : nullptr, *pre = p == 0 ? fz.pre : nullptr;
         const uint64_t *post = p == npass - 1 ? fz.post : nullptr;
-        if (r29 && k >= 2 && ntt4_enabled()) {
-            const uint32_t *pre29 = p == 0 ? fz.pre29 : nullptr, *post29 = p == npass - 1 ? fz.post29 : nullptr;
-            const uint32_t b4 = (uint32_t)((N >> k) / (TILE >> k));
-            switch (k) {
-#define PNP_CASE429(KK)                                                                                 \
-    case KK:                                                                                            \
-        if (dit)                                                                                        \
-            hipLaunchKernelGGL((k_ntt_pass4_29<KK, true>), dim3(b4), dim3(NTT4_THREADS), 0, s, d, tw29, \
-                               lg, lg_hlo, src, pre29, fz.src_mask, post29);                           \
-        else                                                                                            \
-            hipLaunchKernelGGL((k_ntt_pass4_29<KK, false>), dim3(b4), dim3(NTT4_THREADS), 0, s, d, tw29, \
-                               lg, lg_hlo, src, pre29, fz.src_mask, post29);                           \
-        break;
-                PNP_CASE429(2) PNP_CASE429(3) PNP_CASE429(4) PNP_CASE429(5)
-                PNP_CASE429(6) PNP_CASE429(7) PNP_CASE429(8)
-#undef PNP_CASE429
-            }
-            PNP_HIP(hipGetLastError());
-            lo = dit ? lo + k : lo - k;
-            continue;
-        }
-        if (r29 && (!src || pre)) {
-            const uint32_t *pre29 = p == 0 ? fz.pre29 : nullptr, *post29 = p == npass - 1 ? fz.post29 : nullptr;
-            switch (k) {
-#define PNP_CASE29(KK)                                                                              \
-    case KK:                                                                                        \
-        if (dit)                                                                                    \
-            hipLaunchKernelGGL((k_ntt_pass29<KK, true>), dim3(blocks), dim3(NTT_THREADS), 0, s, d, tw29, \
-                               lg, lg_hlo, src, pre29, fz.src_mask, post29);                       \
-        else                                                                                        \
-            hipLaunchKernelGGL((k_ntt_pass29<KK, false>), dim3(blocks), dim3(NTT_THREADS), 0, s, d, tw29, \
-                               lg, lg_hlo, src, pre29, fz.src_mask, post29);                       \
-        break;
-                PNP_CASE29(1) PNP_CASE29(2) PNP_CASE29(3) PNP_CASE29(4)
-                PNP_CASE29(5) PNP_CASE29(6) PNP_CASE29(7) PNP_CASE29(8)
-#undef PNP_CASE29
-            }
-            PNP_HIP(hipGetLastError());
-            lo = dit ? lo + k : lo - k;
-            continue;
-        }
-        if (ntt4_enabled() && k >= 2) {
-            const int rows = ntt_rows_enabled() ? 1 : 0;
-            const uint64_t *tw4 = rows ? ntt_twiddle_rows(t, lg, inverse, s) : tw;
-            switch (k) {
+        // (every caller gives k >= 5: a single pass over count <= 8 blocks needs
+        // count << lg to be whole tiles, so lg >= 7; the balanced split of
+        // lg > LGTILE has no pass under 11 / 2 levels)
+        const int rows = ntt_rows_enabled() ? 1 : 0;
+        const uint64_t *tw4 = rows ? ntt_twiddle_rows(t, lg, inverse, s) : tw;
+        switch (k) {
 #define PNP_CASE4(KK)                                                                               \
     case KK:                                                                                        \
         if (dit)                                                                                    \
@@ -972,36 +553,12 @@ static void ntt_core(NttTables &t, uint64_t *d, uint32_t lg, bool inverse, bool 
             hipLaunchKernelGGL((k_ntt_pass4<KK, false>), dim3(blocks), dim3(NTT4_THREADS), 0, s, d, tw4, \
                                lg, lg_hlo, src, pre, fz.src_mask, post, rows);                     \
         break;
-                PNP_CASE4(2) PNP_CASE4(3) PNP_CASE4(4) PNP_CASE4(5) PNP_CASE4(6)
-                PNP_CASE4(7) PNP_CASE4(8) PNP_CASE4(9) PNP_CASE4(10)
+            PNP_CASE4(2) PNP_CASE4(3) PNP_CASE4(4) PNP_CASE4(5) PNP_CASE4(6)
+            PNP_CASE4(7) PNP_CASE4(8) PNP_CASE4(9) PNP_CASE4(10)
 #if PNP_NTT_LGTILE >= 11
-                PNP_CASE4(11)
+            PNP_CASE4(11)
 #endif
 #undef PNP_CASE4
-                default:
-                    set_error("bad NTT pass size %d", k);
-                    throw Error(PNP_E_ARG);
-            }
-            PNP_HIP(hipGetLastError());
-            lo = dit ? lo + k : lo - k;
-            continue;
-        }
-        switch (k) {
-#define PNP_CASE(KK)                                                                               \
-    case KK:                                                                                       \
-        if (dit)                                                                                   \
-            hipLaunchKernelGGL((k_ntt_pass<KK, true>), dim3(blocks), dim3(NTT_THREADS), 0, s, d, tw, \
-                               lg, lg_hlo, src, pre, fz.src_mask, post);                          \
-        else                                                                                       \
-            hipLaunchKernelGGL((k_ntt_pass<KK, false>), dim3(blocks), dim3(NTT_THREADS), 0, s, d, tw, \
-                               lg, lg_hlo, src, pre, fz.src_mask, post);                          \
-        break;
-            PNP_CASE(1) PNP_CASE(2) PNP_CASE(3) PNP_CASE(4) PNP_CASE(5)
-            PNP_CASE(6) PNP_CASE(7) PNP_CASE(8) PNP_CASE(9) PNP_CASE(10)
-#if PNP_NTT_LGTILE >= 11
-            PNP_CASE(11)
-#endif
-#undef PNP_CASE
             default:
                 set_error("bad NTT pass size %d", k);
                 throw Error(PNP_E_ARG);
@@ -1016,11 +573,8 @@ static void dif(NttTables &t, uint64_t *d, uint32_t lg, bool inverse, hipStream_
 }
 
 static void bitrev(uint64_t *d, uint32_t lg, const Scale &sc, hipStream_t s, uint32_t nblocks = 1) {
-    static const int tb = getenv("PNP_BITREV_TB") && atoi(getenv("PNP_BITREV_TB")) == 5 ? 5 : 4;  // A/B
     if (lg < 10) {
         hipLaunchKernelGGL(k_bitrev_small, dim3(1, nblocks), dim3(256), 0, s, d, lg, sc);
-    } else if (tb == 5) {
-        hipLaunchKernelGGL(k_bitrev_tiles<5>, dim3(1u << (lg - 10), nblocks), dim3(256), 0, s, d, lg, sc);
     } else {
         hipLaunchKernelGGL(k_bitrev_tiles<4>, dim3(1u << (lg - 8), nblocks), dim3(256), 0, s, d, lg, sc);
     }
@@ -1165,19 +719,6 @@ static void check_blocks(int m0, int nb) {
     }
 }
 
-// out[b n + brev(j)] = f(g w_8n^(8 j + m0 + b)), b < nb, for the n
-// coefficients `in`: the twist is fused into the first DIF pass and the DIF's
-// bit-reversed output is kept ("block-bitrev layout", no reversal pass); the
-// quotient's arrays share the layout and intt_blocks undoes it with a DIT.
-static const uint32_t *block_twist_table29(NttTables &t, uint32_t lg_n, bool inverse, hipStream_t s) {
-    return to_r29_table(inverse ? t.blk_twist_inv29 : t.blk_twist29, lg_n, block_twist_table(t, lg_n, inverse, s),
-                        8ULL << lg_n, s);
-}
-// the forward twists times 32 in the 2^261 form (the radix-2^29 LDE into k_quotient29's form)
-static const uint32_t *block_twist_table32_29(NttTables &t, uint32_t lg_n, hipStream_t s) {
-    return to_r29_table(t.blk_twist32_29, lg_n, block_twist_table32(t, lg_n, s), 8ULL << lg_n, s);
-}
-
 // Every table a proof of domain 2^lg_n reads, built on stream s.  The tables
 // are otherwise built lazily by their first user; a proof forks LDEs onto a
 // side stream, so prove_impl builds them on its main stream before the first
@@ -1186,26 +727,22 @@ void ntt_warm(NttTables &t, uint32_t lg_n, hipStream_t s) {
     for (bool inv : {false, true}) {
         ntt_twiddles(t, lg_n, inv, s);
         block_twist_table(t, lg_n, inv, s);
-        if (ntt29_enabled()) {
-            ntt_twiddles29(t, lg_n, inv, s);
-            block_twist_table29(t, lg_n, inv, s);
-        }
     }
     block_twist_table32(t, lg_n, s);
-    if (ntt29_enabled()) block_twist_table32_29(t, lg_n, s);
     ntt_prepare_coset(t, s);
 }
 
+// out[b n + brev(j)] = f(g w_8n^(8 j + m0 + b)), b < nb, for the n
+// coefficients `in`: the twist is fused into the first DIF pass and the DIF's
+// bit-reversed output is kept ("block-bitrev layout", no reversal pass); the
+// quotient's arrays share the layout and intt_blocks undoes it with a DIT.
+// form29: the twists times 32, so the values come out in fr29.cuh's 2^261 form
 void lde_blocks(NttTables &t, const uint64_t *in, uint64_t *out, uint32_t lg_n, int m0, int nb,
                 hipStream_t s, bool form29) {
     const uint64_t n = 1ULL << lg_n;
     PassFuse fz;
     fz.src = in;
-    // (form29: the 32-bit passes; the experimental radix-2^29 passes have no scaled twist)
     fz.pre = (form29 ? block_twist_table32(t, lg_n, s) : block_twist_table(t, lg_n, false, s)) + 4 * (uint64_t)m0 * n;
-    if (ntt29_enabled())
-        fz.pre29 = (form29 ? block_twist_table32_29(t, lg_n, s) : block_twist_table29(t, lg_n, false, s)) +
-                   9 * (uint64_t)m0 * n;
     fz.src_mask = n - 1;
     check_blocks(m0, nb);
     ntt_core(t, out, lg_n, false, false, s, (uint64_t)nb, fz);
@@ -1223,7 +760,6 @@ void intt_blocks(NttTables &t, uint64_t *d, uint32_t lg_n, int m0, int nb, hipSt
     const uint64_t n = 1ULL << lg_n;
     PassFuse fz;
     fz.post = block_twist_table(t, lg_n, true, s) + 4 * (uint64_t)m0 * n;
-    if (ntt29_enabled()) fz.post29 = block_twist_table29(t, lg_n, true, s) + 9 * (uint64_t)m0 * n;
     check_blocks(m0, nb);
     ntt_core(t, d, lg_n, true, true, s, (uint64_t)nb, fz);
 }

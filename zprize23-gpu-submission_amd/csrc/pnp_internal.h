@@ -62,11 +62,8 @@ struct NttTables {
     std::map<uint32_t, DevBuf> lde_twist;
     // block layout twists per lg_n: (g w_8n^m)^j and w_8n^(-m j), block m
     std::map<uint32_t, DevBuf> blk_twist, blk_twist_inv;
-    // the same twiddles / twists times 2^261 in radix 2^29 (9 u32 per entry)
-    // for the radix-2^29 passes (fr29.cuh)
-    std::map<uint32_t, DevBuf> fwd29, inv29, blk_twist29, blk_twist_inv29;
-    // the forward block twists times 32 (lde_blocks form29), and their 2^261 form
-    std::map<uint32_t, DevBuf> blk_twist32, blk_twist32_29;
+    // the forward block twists times 32 (lde_blocks form29)
+    std::map<uint32_t, DevBuf> blk_twist32;
 };
 const uint64_t *ntt_twiddles(NttTables &t, uint32_t lg, bool inverse, hipStream_t s);
 void ntt_prepare_coset(NttTables &t, hipStream_t s);
@@ -152,9 +149,7 @@ struct MsmGroup {
 };
 struct MsmWork {
     DevBuf digits;  // u32 keys of every (MSM, window, point)
-    MsmGroup grp[2];  // the two pipelined groups of a batch
-    hipStream_t s2 = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    MsmGroup grp;
     KernelTimer *timer = nullptr;
     // point-range sharding across ranks (pnp_set_msm_shard)
     // window bits of the folded layout (msm_cfg default when 0; PNP_FOLD_C)
