@@ -1,0 +1,236 @@
+// Microbenchmark: throughput of the Fq Montgomery product on the whole chip,
+// radix 2^29 unsigned (field29.cuh, 392 v_mad_u64_u32) against 13 SIGNED
+// 30-bit limbs, balanced in [-2^29, 2^29), R = 2^390: 338 v_mad_i64_i32 in ONE
+// signed 64-bit column accumulator (26 products of <= 2^58 are < 2^63, so the
+// two accumulators of tools/ubench_fq30.hip are not needed).  Same launch
+// shape and method as tools/ubench_fq30.hip: random operands, every CU busy,
+// best of 5, so the clock the chip holds under the load is part of the result.
+// The signed product is checked first: the host's copy of the function
+// against integer arithmetic mod q, then 256 lanes' chains on the GPU against
+// the host's (check() below).
+//   hipcc -O3 --offload-arch=gfx950 -I<csrc> ubench_fq30s.hip -o ubench_fq30s
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+#include "field29.cuh"
+using namespace pnp;
+
+namespace f30s {
+// q in balanced limbs, sum Q[i] 2^(30 i) = q
+__host__ __device__ constexpr int32_t qlimb(int i) {
+    constexpr int32_t Q[13] = {-21845,    -402915328, 356515836,  -352321620, -252304353, 55215067, 288093811,
+                               316751073, -321428361, 517541167, -375082566, -91332614,  1704210};
+    return Q[i];
+}
+constexpr uint32_t QINV = 0xfffcfffdu;  // -q^-1 mod 2^30, sign-extended (-196611)
+struct F30 {
+    int32_t l[13];
+};
+// low 30 bits of x as a balanced limb in [-2^29, 2^29)
+__host__ __device__ __forceinline__ int32_t bal30(uint32_t x) { return (int32_t)(x << 2) >> 2; }
+__host__ __device__ __forceinline__ int64_t mad(int32_t a, int32_t b, int64_t acc) { return acc + (int64_t)a * b; }
+// a b 2^-390 (mod q), |a|, |b| < 2^385 -> |r| < 2^381; r.l[0..11] balanced
+__host__ __device__ __forceinline__ F30 mul(const F30 &a, const F30 &b) {
+    int32_t m[13];
+    F30 r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 25; k++) {
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) acc = mad(a.l[i], b.l[k - i], acc);
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); i < (k < 13 ? k : 13); i++) acc = mad(m[i], qlimb(k - i), acc);
+        if (k < 13) {
+            m[k] = bal30((uint32_t)acc * QINV);
+            acc = mad(m[k], qlimb(0), acc);  // low 30 bits become 0
+            acc >>= 30;
+        } else {
+            r.l[k - 13] = bal30((uint32_t)acc);
+            acc = (acc + (1 << 29)) >> 30;
+        }
+    }
+    r.l[12] = (int32_t)acc;
+    return r;
+}
+}  // namespace f30s
+
+__global__ __launch_bounds__(256) void k_mul29(uint32_t *out, int L, uint32_t seed) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    F29 a, b, c, d;
+    uint32_t h = seed ^ (t * 0x9E3779B9u);
+    for (int i = 0; i < 14; i++) {
+        h = h * 1664525u + 1013904223u; a.l[i] = h & F29_M;
+        h = h * 1664525u + 1013904223u; b.l[i] = h & F29_M;
+        h = h * 1664525u + 1013904223u; c.l[i] = h & F29_M;
+        h = h * 1664525u + 1013904223u; d.l[i] = h & F29_M;
+    }
+    a.l[13] &= 0xFFFFFF; b.l[13] &= 0xFFFFFF; c.l[13] &= 0xFFFFFF; d.l[13] &= 0xFFFFFF;
+#pragma unroll 1
+    for (int i = 0; i < L; i++) {
+        a = mul29(a, b); c = mul29(c, d); b = mul29(b, c); d = mul29(d, a);
+    }
+    uint32_t x = 0;
+    for (int i = 0; i < 14; i++) x ^= a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i];
+    out[t] = x;
+}
+
+// the four operands of lane t: balanced limbs, top limb < 2^21 in magnitude
+__host__ __device__ inline void seed30s(uint32_t t, uint32_t seed, f30s::F30 &a, f30s::F30 &b, f30s::F30 &c,
+                                        f30s::F30 &d) {
+    uint32_t h = seed ^ (t * 0x9E3779B9u);
+    for (int i = 0; i < 13; i++) {
+        h = h * 1664525u + 1013904223u; a.l[i] = f30s::bal30(h >> 2);
+        h = h * 1664525u + 1013904223u; b.l[i] = f30s::bal30(h >> 2);
+        h = h * 1664525u + 1013904223u; c.l[i] = f30s::bal30(h >> 2);
+        h = h * 1664525u + 1013904223u; d.l[i] = f30s::bal30(h >> 2);
+    }
+    a.l[12] >>= 8; b.l[12] >>= 8; c.l[12] >>= 8; d.l[12] >>= 8;
+}
+__host__ __device__ inline void chain30s(int L, f30s::F30 &a, f30s::F30 &b, f30s::F30 &c, f30s::F30 &d) {
+#pragma unroll 1
+    for (int i = 0; i < L; i++) {
+        a = f30s::mul(a, b); c = f30s::mul(c, d); b = f30s::mul(b, c); d = f30s::mul(d, a);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mul30s(uint32_t *out, int L, uint32_t seed) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    f30s::F30 a, b, c, d;
+    seed30s(t, seed, a, b, c, d);
+    chain30s(L, a, b, c, d);
+    uint32_t x = 0;
+    for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
+    out[t] = x;
+}
+
+// ---- host check of the signed product ------------------------------------
+// r = a b 2^-390 (mod q) means r 2^390 - a b = 0 (mod q): the 780-bit integer
+// is formed in 30-bit limbs and divided by q bit by bit.
+static bool divisible_by_q(std::vector<int64_t> v) {  // v: signed limbs radix 2^30, little endian
+    static const uint64_t QW[7] = {0xb9feffffffffaaabull, 0x1eabfffeb153ffffull, 0x6730d2a0f6b0f624ull,
+                                   0x64774b84f38512bfull, 0x4b1ba7b6434bacd7ull, 0x1a0111ea397fe69aull, 0};
+    // normalise the limbs; a negative integer is negated (divisibility does not depend on the sign)
+    int64_t c = 0;
+    for (auto &x : v) { x += c; c = x >> 30; x &= 0x3FFFFFFF; }
+    if (c < 0) {  // negate: two's complement over the limbs
+        int64_t b = 1;
+        for (auto &x : v) { x = (~x & 0x3FFFFFFF) + b; b = x >> 30; x &= 0x3FFFFFFF; }
+        c = ~c + b;
+    }
+    v.push_back(c);
+    const int nb = 30 * (int)v.size();
+    std::vector<uint8_t> bits(nb);
+    for (int i = 0; i < nb; i++) bits[i] = (v[i / 30] >> (i % 30)) & 1;
+    // remainder in 7 x 64-bit words, shift-and-subtract from the top bit
+    uint64_t rem[7] = {0};
+    for (int i = nb - 1; i >= 0; i--) {
+        for (int w = 6; w > 0; w--) rem[w] = (rem[w] << 1) | (rem[w - 1] >> 63);
+        rem[0] = (rem[0] << 1) | bits[i];
+        bool ge = true;
+        for (int w = 6; w >= 0; w--)
+            if (rem[w] != QW[w]) { ge = rem[w] > QW[w]; break; }
+        if (ge) {
+            uint64_t bw = 0;
+            for (int w = 0; w < 7; w++) {
+                const uint64_t s = rem[w] - QW[w] - bw;
+                bw = (rem[w] < QW[w] + bw) || (QW[w] + bw < bw);
+                rem[w] = s;
+            }
+        }
+    }
+    for (int w = 0; w < 7; w++)
+        if (rem[w]) return false;
+    return true;
+}
+static bool check_product(const f30s::F30 &a, const f30s::F30 &b) {
+    const f30s::F30 r = f30s::mul(a, b);
+    std::vector<int64_t> v(27, 0);  // r 2^390 - a b, columns of 13 products < 2^58 and one limb
+    for (int i = 0; i < 13; i++) v[13 + i] += r.l[i];
+    for (int i = 0; i < 13; i++)
+        for (int j = 0; j < 13; j++) v[i + j] -= (int64_t)a.l[i] * b.l[j];
+    for (int i = 0; i < 12; i++)
+        if (r.l[i] < -(1 << 29) || r.l[i] >= (1 << 29)) return false;
+    return divisible_by_q(v);
+}
+static bool check(uint32_t *dout) {
+    f30s::F30 a, b, c, d;
+    int bad = 0;
+    for (uint32_t t = 0; t < 64; t++) {
+        seed30s(t, 99u, a, b, c, d);
+        for (int i = 0; i < 8; i++) {
+            bad += !check_product(a, b); a = f30s::mul(a, b);
+            bad += !check_product(c, d); c = f30s::mul(c, d);
+            bad += !check_product(b, c); b = f30s::mul(b, c);
+            bad += !check_product(d, a); d = f30s::mul(d, a);
+        }
+    }
+    for (int s = 0; s < 4; s++) {  // every limb at an end of its range
+        for (int i = 0; i < 13; i++) {
+            a.l[i] = (s & 1) ? -(1 << 29) : (1 << 29) - 1;
+            b.l[i] = (s & 2) ? -(1 << 29) : (1 << 29) - 1;
+        }
+        a.l[12] >>= 5; b.l[12] >>= 5;  // |value| < 2^385
+        bad += !check_product(a, b);
+    }
+    printf("signed product against integer arithmetic mod q on the host: %s\n", bad ? "MISMATCH" : "ok");
+    if (dout) {  // the GPU's chain of lanes 0..255 against the host's
+        hipLaunchKernelGGL(k_mul30s, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+        uint32_t g[256];
+        if (hipMemcpy(g, dout, sizeof g, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        int gb = 0;
+        for (uint32_t t = 0; t < 256; t++) {
+            seed30s(t, 5u, a, b, c, d);
+            chain30s(3, a, b, c, d);
+            uint32_t x = 0;
+            for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
+            gb += x != g[t];
+        }
+        printf("GPU chain against the host's, 256 lanes: %s\n", gb ? "MISMATCH" : "ok");
+        bad += gb;
+    }
+    return bad == 0;
+}
+
+template <typename K>
+static double run(K kern, const char *name, uint32_t *dout, uint32_t threads, int L) {
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    hipLaunchKernelGGL(kern, dim3(threads / 256), dim3(256), 0, 0, dout, 4, 1u);
+    hipDeviceSynchronize();
+    float best = 1e30f, worst = 0;
+    for (int rep = 0; rep < 5; rep++) {
+        hipEventRecord(e0);
+        hipLaunchKernelGGL(kern, dim3(threads / 256), dim3(256), 0, 0, dout, L, 7u + rep);
+        hipEventRecord(e1);
+        hipEventSynchronize(e1);
+        float ms;
+        hipEventElapsedTime(&ms, e0, e1);
+        if (ms < best) best = ms;
+        if (ms > worst) worst = ms;
+    }
+    hipFuncAttributes fa;
+    hipFuncGetAttributes(&fa, (const void *)kern);
+    const double prods = 4.0 * L * threads;
+    printf("%-8s best %8.3f ms  worst %8.3f ms  %7.2f G products/s  (%d VGPRs)\n", name, best, worst,
+           prods / best / 1e6, fa.numRegs);
+    return prods / best / 1e6;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "--host-check")) return check(nullptr) ? 0 : 1;
+    const uint32_t threads = 1u << 20;
+    const int L = 256;
+    uint32_t *dout;
+    if (hipMalloc(&dout, threads * 4) != hipSuccess) return 2;
+    if (!check(dout)) return 1;
+    double a[3], b[3];
+    for (int i = 0; i < 3; i++) {
+        a[i] = run(k_mul29, "mul29", dout, threads, L);
+        b[i] = run(k_mul30s, "mul30s", dout, threads, L);
+    }
+    for (int i = 0; i < 3; i++) printf("ratio mul30s / mul29 = %.3f\n", b[i] / a[i]);
+    return 0;
+}

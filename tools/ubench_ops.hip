@@ -69,10 +69,16 @@ __global__ void k_cnd_cmp(uint64_t *out, uint32_t a) {
     }
 #define I_MAD64(r) "v_mad_u64_u32 " r ", s[20:21], %8, %9, " r "\n"
 #define I_MAD64V(r) "v_mad_u64_u32 " r ", vcc, %8, %9, " r "\n"
+#define I_MADI64(r) "v_mad_i64_i32 " r ", s[20:21], %8, %9, " r "\n"
+#define I_ASHR64(r) "v_ashrrev_i64 " r ", 30, " r "\n"
+#define I_BFE(r) "v_bfe_i32 " r ", " r ", 0, 30\n"
 #define I_SHR64(r) "v_lshrrev_b64 " r ", 29, " r "\n"
 #define I_LADD64(r) "v_lshl_add_u64 " r ", " r ", 0, " r "\n"
 K64(k_mad64, I_MAD64)
 K64(k_mad64v, I_MAD64V)
+K64(k_madi64, I_MADI64)
+K64(k_ashr64, I_ASHR64)
+K32(k_bfe, I_BFE)
 K64(k_shr64, I_SHR64)
 K64(k_ladd64, I_LADD64)
 
@@ -117,6 +123,7 @@ int main() {
         {"v_mul_lo_u32", k_mullo, 64}, {"v_mad_u32_u24", k_mad24, 64}, {"v_cndmask_b32", k_cnd, 64}, {"v_cndmask_b32_e64(sgpr)", k_cnd64, 64},
         {"v_subb_co_u32(vcc)", k_subb, 64}, {"v_cmp+v_cndmask pair", k_cnd_cmp, 32},
         {"v_mad_u64_u32(sdst)", k_mad64, 64}, {"v_mad_u64_u32(vcc)", k_mad64v, 64},
+        {"v_mad_i64_i32(sdst)", k_madi64, 64}, {"v_ashrrev_i64", k_ashr64, 64}, {"v_bfe_i32", k_bfe, 64},
         {"v_lshrrev_b64", k_shr64, 64}, {"v_lshl_add_u64", k_ladd64, 64}, {"v_fma_f64", k_fma64, 64}};
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);

@@ -39,6 +39,7 @@
 #include "msm_internal.h"
 #include "ec.cuh"
 #include "ec29.cuh"
+#include "field30s.cuh"
 
 namespace pnp {
 
@@ -807,47 +808,95 @@ __global__ __launch_bounds__(256) void k_accumulate_flat(const uint64_t *points,
     segment32(t, ld, st, sorted, offs, nch, U, S);
 }
 
-// ---- radix-2^29 accumulation (field29.cuh) over the folded table in F29 form
-// (28 u32 per point: x, y in R = 2^406 Montgomery, < 2q)
-// (load29, Xyzz29: ec29.cuh)
-// P += (x2, y2), madd-2008-s.  Bounds (see field29.cuh): products < 2^382,
-// stored coordinates < 2^389, every product input < 2^391 (Y3 < 2^382 comes
-// from mul2_29).  No equal /
+// ---- signed radix-2^30 accumulation (field30s.cuh) over the folded table in
+// F30s form (26 u32 per point: x, y in R = 2^390 Montgomery, |.| < 2^381)
+struct Xyzz30s {
+    F30s x, y, zz, zzz;
+};
+// P += (x2, y2), madd-2008-s.  Bounds (see field30s.cuh; the interval
+// analysis of tests/test_field30s.py): x2, y2 and every product output are
+// < 2^381 in magnitude, X3 = R^2 - PPP - 2 Q < 2^383, P = U2 - X < 2^383.4,
+// R = S2 - Y < 2^382, Q - X3 < 2^383.4 — every product input < 2^385, and Y3
+// (one reduction of two products < 2^766 + 2^762) < 2^381 again.  No equal /
 // opposite / infinity cases: those make ZZ = 0 mod q, detected per piece.
-__device__ __forceinline__ void madd29(Xyzz29 &p, const F29 &x2, const F29 &y2) {
-    F29 u2 = mul29(x2, p.zz);
-    F29 s2 = mul29(y2, p.zzz);
-    F29 P = sub29(u2, p.x, F29_KB);
-    F29 R = sub29(s2, p.y, F29_KB);
-    F29 pp = sqr29(P);
-    F29 ppp = mul29(P, pp);
-    F29 q = mul29(p.x, pp);
-    F29 x3 = sub29(sub29(sub29(sqr29(R), ppp, F29_KA), q, F29_KA), q, F29_KA);
-    // Y3 = R (Q - X3) - Y PPP as R (Q - X3) + Y (KA - PPP), one reduction
-    F29 y3 = mul2_29(R, sub29(q, x3, F29_KB), p.y, neg29(ppp, F29_KA));
-    p.zz = mul29(p.zz, pp);
-    p.zzz = mul29(p.zzz, ppp);
+// 6 mul30s + 2 sqr30s + mul2_30s = 6 338 + 2 260 + 507 = 3,055 multiply-adds
+// (the radix-2^29 form: 6 392 + 2 301 + 588 = 3,542).
+__device__ __forceinline__ void madd30s(Xyzz30s &p, const F30s &x2, const F30s &y2) {
+    F30s u2 = mul30s(x2, p.zz);
+    F30s s2 = mul30s(y2, p.zzz);
+    F30s P = sub30s(u2, p.x);
+    F30s R = sub30s(s2, p.y);
+    F30s pp = sqr30s(P);
+    F30s ppp = mul30s(P, pp);
+    F30s q = mul30s(p.x, pp);
+    // two passes: a limb of R^2 - PPP - 2 Q could reach 2^31
+    F30s x3 = sub30s(sub2_30s(sqr30s(R), ppp, q), q);
+    // Y3 = R (Q - X3) - Y PPP as R (Q - X3) + Y (-PPP), one reduction
+    F30s y3 = mul2_30s(R, sub30s(q, x3), p.y, neg30s(ppp));
+    p.zz = mul30s(p.zz, pp);
+    p.zzz = mul30s(p.zzz, ppp);
     p.x = x3;
     p.y = y3;
 }
 // Pieces leave the accumulation in raw radix-2^29 form (56 u32 per XYZZ
 // point, 4 x 14 limbs, ec29.cuh) and stay in it through the merge and the
 // reduction tree (msm_reduce.hip); only the roots are converted to R384.
-// raw store; false when ZZ = 0 mod q (a degenerate step in the piece)
-__device__ __forceinline__ bool store29(uint32_t *dst, const Xyzz29 &p) {
-    store_f29(dst, p.x);
-    store_f29(dst + 14, p.y);
-    store_f29(dst + 28, p.zz);
-    store_f29(dst + 42, p.zzz);
-    return !zero29(p.zz);
+// The accumulator is in F30s form, so each coordinate of a piece is converted
+// (to_f29: one product by a constant and a repack, 4 x 338 multiply-adds a
+// piece against the 3,055 of an addition, on the ~1.3% of entries that end a
+// piece: ~0.6%).  Not where the piece ends: a bucket ends in some lane of a
+// wave in about every second step of its loop, and the whole wave would wait
+// for that lane's four products.  The loop leaves the piece in its slot as it
+// is (park30s: 52 of the slot's 56 u32), and the lane converts its slots in
+// place when its segment is done (store29 over the same walk of the buckets).
+__device__ __forceinline__ void park30s(uint32_t *dst, const Xyzz30s &p) {
+    uint32_t w[52];
+#pragma unroll
+    for (int i = 0; i < 13; i++) {
+        w[i] = (uint32_t)p.x.l[i];
+        w[13 + i] = (uint32_t)p.y.l[i];
+        w[26 + i] = (uint32_t)p.zz.l[i];
+        w[39 + i] = (uint32_t)p.zzz.l[i];
+    }
+    uint4 *q = reinterpret_cast<uint4 *>(dst);
+#pragma unroll
+    for (int c = 0; c < 13; c++) q[c] = make_uint4(w[4 * c], w[4 * c + 1], w[4 * c + 2], w[4 * c + 3]);
+}
+// parked F30s piece -> raw F29 piece, in place; false when ZZ = 0 mod q (a
+// degenerate step in the piece)
+__device__ __forceinline__ bool store29(uint32_t *dst) {
+    uint32_t w[52];
+    const uint4 *q = reinterpret_cast<const uint4 *>(dst);
+#pragma unroll
+    for (int c = 0; c < 13; c++) {
+        const uint4 v = q[c];
+        w[4 * c] = v.x;
+        w[4 * c + 1] = v.y;
+        w[4 * c + 2] = v.z;
+        w[4 * c + 3] = v.w;
+    }
+    Xyzz30s p;
+#pragma unroll
+    for (int i = 0; i < 13; i++) {
+        p.x.l[i] = (int32_t)w[i];
+        p.y.l[i] = (int32_t)w[13 + i];
+        p.zz.l[i] = (int32_t)w[26 + i];
+        p.zzz.l[i] = (int32_t)w[39 + i];
+    }
+    const F29 zz = to_f29(p.zz);
+    store_f29(dst, to_f29(p.x));
+    store_f29(dst + 14, to_f29(p.y));
+    store_f29(dst + 28, zz);
+    store_f29(dst + 42, to_f29(p.zzz));
+    return !zero29(zz);
 }
 
 #ifndef PNP_ACC_WAVES
 #define PNP_ACC_WAVES 3
 #endif
-// Folded-table entry stride in u32: x, y (14 limbs each) padded to 128 B so a
-// gathered point is exactly one cache line (112 B at a 112 B stride straddles
-// two lines in 7 of 8 cases)
+// Folded-table entry stride in u32: x, y (13 limbs each, 104 B) padded to
+// 128 B so a gathered point is exactly one cache line (a 104 B stride would
+// straddle two lines most of the time)
 #ifndef PNP_PT29
 #define PNP_PT29 32
 #endif
@@ -866,7 +915,7 @@ __device__ __forceinline__ void stage_point(const uint32_t *p, uint4 *st) {
     for (int c = 0; c < 7; c++)
         __builtin_amdgcn_global_load_lds((glob_void_t *)(p + 4 * c), (lds_void_t *)(st + 64 * c), 16, 0, 0);
 }
-__device__ __forceinline__ void unstage_point(const uint4 *st, F29 &x, F29 &y) {
+__device__ __forceinline__ void unstage_point(const uint4 *st, F30s &x, F30s &y) {
     uint32_t w[28];
 #pragma unroll
     for (int c = 0; c < 7; c++) {
@@ -877,9 +926,9 @@ __device__ __forceinline__ void unstage_point(const uint4 *st, F29 &x, F29 &y) {
         w[4 * c + 3] = v.w;
     }
 #pragma unroll
-    for (int i = 0; i < 14; i++) {
-        x.l[i] = w[i];
-        y.l[i] = w[14 + i];
+    for (int i = 0; i < 13; i++) {
+        x.l[i] = (int32_t)w[i];
+        y.l[i] = (int32_t)w[13 + i];
     }
 }
 
@@ -896,9 +945,11 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
     const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     uint4 *wave_base = stage + 7 * 64 * wv;
     uint32_t *idx_base = sidx + 64 * wv;
-    uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    // lane and bucket numbers in 32 bits: they live across the loop, whose
+    // addition leaves no register to spare at 3 waves per SIMD
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t total = offs[U];
-    const uint64_t lo64 = t * S;
+    const uint64_t lo64 = (uint64_t)t * S;
     if (lo64 >= total) return;
     const uint32_t lo = (uint32_t)lo64;
     const uint32_t hi = lo + S < total ? lo + S : total;
@@ -907,23 +958,25 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
         uint64_t m = (a + b) >> 1;
         if (offs[m] <= lo) a = m; else b = m;
     }
-    uint64_t cur = a;
+    uint32_t cur = (uint32_t)a;
     bool first = offs[cur] < lo;
     uint32_t next = offs[cur + 1];
     bool ok = true, fresh = true;
-    Xyzz29 acc;
+    Xyzz30s acc;
     uint32_t e = sorted[lo];
     stage_point(pts29 + PT29 * (e & 0x7FFFFFFFu), wave_base);
     if (lo + 1 < hi)
         __builtin_amdgcn_global_load_lds((glob_void_t *)(sorted + lo + 1), (lds_void_t *)idx_base, 4, 0, 0);
     for (uint32_t k = lo; k < hi; k++) {
         if (k == next) {
-            ok &= store29(first ? head + 56 * t : buckets + 56 * cur, acc);
+            // (slot address from a selected base and index: the lane's head
+            // address, loop-invariant, would be hoisted and spilled)
+            park30s((first ? head : buckets) + 56ull * (first ? t : cur), acc);
             first = false;
             fresh = true;
-            cur = next_bucket(offs, 1, U, cur + 1, k, next);
+            cur = (uint32_t)next_bucket(offs, 1, U, (uint64_t)cur + 1, k, next);
         }
-        F29 x, y;
+        F30s x, y;
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): point k and index k+1 have landed
         unstage_point(wave_base + ln, x, y);
         const uint32_t en = idx_base[ln];
@@ -936,21 +989,43 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
                                                  0);
             e = en;
         }
-        if (ecur >> 31) y = neg29(y, F29_KA);
+        if (ecur >> 31) y = neg30s(y);
         if (fresh) {
             acc.x = x;
             acc.y = y;
-            acc.zz = acc.zzz = const29(F29_ONE);
+            acc.zz = acc.zzz = const30s(F30S_ONE);
             fresh = false;
         } else {
-            madd29(acc, x, y);
+            madd30s(acc, x, y);
         }
     }
     // a bucket continuing past this segment leaves its first piece in tail[t];
     // tailb[t] names it for the merge (one merge lane per accumulation lane)
     const bool to_tail = !first && next > hi;
-    ok &= store29(first ? head + 56 * t : (to_tail ? tail + 56 * t : buckets + 56 * cur), acc);
-    tailb[t] = to_tail ? (uint32_t)cur : NO_TAIL;
+    park30s(first ? head + 56ull * t : (to_tail ? tail + 56ull * t : buckets + 56ull * cur), acc);
+    tailb[t] = to_tail ? cur : NO_TAIL;
+    // the parked pieces to raw F29, over the loop's walk of the buckets again:
+    // a piece that ends before hi went to head[t] (the lane's first) or to its
+    // bucket, the last one as above
+    {
+        // (the first bucket searched for again: kept, it would be live, and
+        // spilled, across the loop)
+        const uint32_t lo2 = t * S;
+        uint64_t c2 = 0, b2 = U;
+        while (b2 - c2 > 1) {
+            uint64_t m = (c2 + b2) >> 1;
+            if (offs[m] <= lo2) c2 = m; else b2 = m;
+        }
+        const uint32_t tot2 = offs[U], hi2 = lo2 + S < tot2 ? lo2 + S : tot2;
+        bool f2 = offs[c2] < lo2;
+        uint32_t n2 = offs[c2 + 1];
+        for (;;) {
+            ok &= store29(f2 ? head + 56ull * t : (n2 > hi2 ? tail + 56ull * t : buckets + 56 * c2));
+            if (n2 >= hi2) break;
+            f2 = false;
+            c2 = next_bucket(offs, 1, U, c2 + 1, n2, n2);
+        }
+    }
     // the lanes with a tail, compacted (tlist[0] = count, then lane ids; one
     // atomic per wave): the merge runs one lane per listed tail instead of one
     // per accumulation lane, ~2/3 of which have none
@@ -961,9 +1036,9 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
         uint32_t base = 0;
         if (below == 0) base = atomicAdd(tlist, (uint32_t)__popcll(m));
         base = __shfl(base, leader);
-        tlist[1 + base + below] = (uint32_t)t;
+        tlist[1 + base + below] = t;
     }
-    if (!ok) redo[atomicAdd(nredo, 1u)] = (uint32_t)t;
+    if (!ok) redo[atomicAdd(nredo, 1u)] = t;
 }
 
 // Work of one k_accumulate29 launch (timed runs only, pnp_kernel_timing): the
@@ -1008,8 +1083,8 @@ __global__ __launch_bounds__(64) void k_accumulate_redo(const uint32_t *pts29, c
     // grid-stride over the flagged lanes (none for random inputs: a small grid
     // that exits at once instead of one lane per accumulation lane)
     auto ld = [pts29](uint32_t i, Fq &x, Fq &y) {
-        x = to_fq32(load29(pts29 + PT29 * i));
-        y = to_fq32(load29(pts29 + PT29 * i + 14));
+        x = to_fq32(load30s(pts29 + PT29 * i));
+        y = to_fq32(load30s(pts29 + PT29 * i + 13));
     };
     auto st = [=](int where, uint64_t i, const Xyzz &p) {
         uint32_t *d = (where == 0 ? buckets : where == 1 ? head : tail) + 56 * i;
@@ -1077,12 +1152,12 @@ __global__ __launch_bounds__(256) void k_table_affine(const uint64_t *xyzz, uint
 __global__ void k_table_to29(const uint64_t *T, uint64_t count, uint32_t *T29) {
     uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (i >= count) return;
-    F29 x = from_fq32(load_fq(T + 12 * i)), y = from_fq32(load_fq(T + 12 * i + 6));
+    F30s x = to_f30s(load_fq(T + 12 * i)), y = to_f30s(load_fq(T + 12 * i + 6));
     uint32_t *o = T29 + PT29 * i;
 #pragma unroll
-    for (int j = 0; j < 14; j++) {
-        o[j] = x.l[j];
-        o[14 + j] = y.l[j];
+    for (int j = 0; j < 13; j++) {
+        o[j] = (uint32_t)x.l[j];
+        o[13 + j] = (uint32_t)y.l[j];
     }
 }
 

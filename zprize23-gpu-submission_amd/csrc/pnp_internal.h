@@ -235,8 +235,8 @@ uint64_t msm_work_bytes(uint64_t n_pts, uint64_t n_cfg, int fold_c, int B, uint6
 uint64_t msm_work_held(const MsmWork &wk);
 // multi-GPU MSMs: the points [p0, p1) rank `rank` of `world` takes
 void msm_point_range(uint64_t n, int rank, int world, uint64_t &p0, uint64_t &p1);
-// T[k*n + i] = 2^(c*k) P_i, k < W (msm_cfg(n)), affine, in the radix-2^29
-// form of field29.cuh (x, y: 14 u32 each, padded to 128 B per point)
+// T[k*n + i] = 2^(c*k) P_i, k < W (msm_cfg(n)), affine, in the signed
+// radix-2^30 form of field30s.cuh (x, y: 13 i32 each, padded to 128 B per point)
 void msm_build_table(DevBuf &tab, const uint64_t *d_points, uint64_t n, int c, hipStream_t s);
 // n device XYZZ points (24 u64) -> affine (12 u64; infinity -> (0, 0)), synchronous
 void xyzz_to_affine_dev(const uint64_t *xyzz, uint64_t n, uint64_t *aff, hipStream_t s);
