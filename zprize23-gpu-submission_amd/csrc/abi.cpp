@@ -627,7 +627,7 @@ hipStream_t pnp_ctx::side_stream() {
 
 uint64_t *pnp_ctx::buf(const std::string &name, size_t elems_fr) {
     auto &b = work[name];
-    if (b.bytes < elems_fr * 32) b.alloc(elems_fr * 32);
+    b.reserve(elems_fr * 32);
     return b.u64();
 }
 

@@ -76,7 +76,7 @@ void k_gather_witness(const uint32_t *const d_var[4], uint64_t n_gates, const ui
 
 uint64_t k_first_diff4(const uint64_t *const a[4], const uint64_t *const b[4], uint32_t lg, DevBuf &scratch,
                        hipStream_t s) {
-    if (scratch.bytes < 8) scratch.alloc(8);
+    scratch.reserve(8);
     unsigned long long *first = static_cast<unsigned long long *>(scratch.p);
     PNP_HIP(hipMemsetAsync(first, 0xff, 8, s));
     DiffArgs c{{a[0], a[1], a[2], a[3]}, {b[0], b[1], b[2], b[3]}};

@@ -35,7 +35,11 @@
 //   6. msm_reduce       : sum_b (b+1) B_b per virtual window (msm_reduce.hip).
 //   7. host             : per-window layout: Horner over the windows; both:
 //                         sum of the ranks' partial results, affine.
+//
+// Host driver (the last section): msm_run_batch -> msm_local_batch, or
+// msm_bucket_batch (bucket_slots, bucket_variable) with every point on each rank.
 #include <algorithm>
+#include <functional>
 #include "msm_internal.h"
 #include "ec.cuh"
 #include "ec29.cuh"
@@ -249,7 +253,7 @@ static void scan_u32(uint32_t *d, uint64_t n, DevBuf &scratch, hipStream_t s) {
     std::vector<std::pair<uint32_t *, uint64_t>> levels;
     uint64_t need = 0, m = n;
     while (m > 1) { m = (m + 1023) / 1024; need += m; }
-    if (scratch.bytes < (need + 1) * 4) scratch.alloc((need + 1) * 4);
+    scratch.reserve((need + 1) * 4);
     uint32_t *p = static_cast<uint32_t *>(scratch.p);
     uint32_t *cur = d;
     m = n;
@@ -1048,8 +1052,7 @@ __global__ __launch_bounds__(256, PNP_ACC_WAVES) void k_accumulate29(const uint3
 // mixed addition: madds = E - pieces.  ctr[0] = E, ctr[1 + (block & 63)] +=
 // the block's pieces (64 counters: one atomic per 1024 buckets, spread, so
 // the ~2M-bucket launch takes microseconds, not the ~0.3 ms one contended
-// counter cost); the host sums them.
-constexpr int WCTR_SLOTS = 64;
+// counter cost); the host sums them.  (WCTR_SLOTS: msm_internal.h)
 __global__ __launch_bounds__(1024) void k_count_pieces(const uint32_t *offs, uint64_t WB, uint32_t S,
                                                        unsigned long long *ctr) {
     __shared__ uint32_t part[16];
@@ -1225,61 +1228,108 @@ static Xyzz get_xyzz(const uint64_t *e) {
     return p;
 }
 
-// B independent MSMs over the same n points, on this GPU only; the B results
-// (XYZZ) land in h_xyzz.  Per-window layout: the B*W windows are "virtual
-// windows" of NB buckets each.  Folded layout (table != nullptr): virtual
-// window b = MSM b with the W key rows of its windows, one bucket set.
 // ---- one group of virtual windows: sort, accumulate (+ merge), reduce
 struct GroupPlan {
     KeyRows kr;
     int nv;  // virtual windows (bucket sets)
 };
 
-// scalars != nullptr: the keys are not made yet; k_digits_hist makes them
-// (standard folded layout: gp.kr covers every window of MSMs 0 .. nv-1)
-static void sort_group(MsmWork &wk, MsmGroup &gb, const uint32_t *keys, const GroupPlan &gp,
-                       const MsmCfg &g, hipStream_t s, const uint64_t *const *scalars = nullptr) {
+// A folded table over n_table points with c-bit windows (0: msm_cfg's choice
+// / MsmWork::fold_c) and the part a batch reads: points [id_base, id_base + n)
+// (a rank's range of a whole table), MSM b from seg_off[b] of every row
+// (MsmSegs).  table = nullptr: the per-window layout over n_table points.
+struct TableView {
+    const uint64_t *table;
+    uint64_t n_table, id_base;
+    const uint64_t *seg_off;
+    int c;
+    MsmCfg cfg(const MsmWork &wk) const { return msm_cfg(n_table, table ? (c ? c : wk.fold_c) : 0, table != nullptr); }
+};
+
+// key rows of nv folded MSMs over n points: MSM v reads the W rows of its windows
+static KeyRows folded_rows(uint64_t n, int nv, const MsmCfg &g, const TableView &tv) {
+    KeyRows kr;
+    kr.n = n, kr.vstride = kr.rows = g.W, kr.off = 0, kr.id_row0 = 0, kr.id_mul = tv.n_table, kr.id_base = tv.id_base;
+    kr.nseg = tv.seg_off ? nv : 0;  // MSM v starts at seg_off[v]
+    for (int v = 0; v < kr.nseg; v++) kr.seg_off[v] = tv.seg_off[v];
+    return kr;
+}
+
+// Pass A over n points and nv virtual windows of c-bit digits: ~512 workgroups
+// in all, >= 1024 points each (nch chunks per window; one, empty, at n = 0);
+// the c - 1 bucket bits split into cb coarse (NBc bins) and fb fine ones
+struct PassA {
+    uint64_t chunk;
+    int nch, cb, fb, NBc;
+    PassA(uint64_t n, int nv, int c) {
+        const int nch0 = std::max(1, 512 / std::max(nv, 1));
+        chunk = std::max<uint64_t>(1024, (n + nch0 - 1) / nch0);
+        nch = (int)std::max<uint64_t>(1, (n + chunk - 1) / chunk);
+        cb = std::min(SORT_CB, c - 1), fb = c - 1 - cb, NBc = 1 << cb;
+    }
+    bool sortable() const { return fb <= SORT_FB_MAX; }  // pass B takes the fine bits in one workgroup
+};
+
+// Digits (returned, in wk.digits; made by the histogram pass for a folded
+// batch of <= ScalarPtrs::MAX MSMs), coarse histogram and scan into gb.counts
+// (run starts, then the total).  wmaj > 1 (bucket ranges): destination-major
+// counts, zeroed first: a rank's empty point range (n = 0) launches nothing
+static const uint32_t *pass_a_count(MsmWork &wk, MsmGroup &gb, const PassA &pa, const GroupPlan &gp, const MsmCfg &g,
+                                    const uint64_t *const *sc, int B, bool folded, int wmaj, hipStream_t s) {
+    const uint64_t n = gp.kr.n;
+    wk.digits.reserve((uint64_t)g.W * B * std::max<uint64_t>(n, 1) * 4);
+    uint32_t *keys = wk.digits.u32();
+    const bool fuse = folded && B <= ScalarPtrs::MAX;
+    for (int b = 0; b < B && n && !fuse; b++) {
+        hipLaunchKernelGGL(k_digits, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sc[b], n, g.c, g.W,
+                           g.top_sh, keys + (uint64_t)b * g.W * n);
+        PNP_HIP(hipGetLastError());
+    }
+    const uint64_t ncount = (uint64_t)gp.nv * pa.NBc * pa.nch;
+    gb.counts.reserve((ncount + 1) * 4);
+    uint32_t *counts = gb.counts.u32();
+    if (wmaj > 1) PNP_HIP(hipMemsetAsync(counts, 0, (ncount + 1) * 4, s));
+    const dim3 grid((uint32_t)pa.nch, (uint32_t)gp.nv);
+    if (n && fuse) {
+        ScalarPtrs sp{};
+        for (int b = 0; b < B; b++) sp.p[b] = sc[b];
+        hipLaunchKernelGGL(k_digits_hist, grid, dim3(1024), 0, s, sp, n, g.c, g.W, g.top_sh, pa.fb, pa.NBc, pa.chunk,
+                           pa.nch, keys, counts, wmaj);
+        PNP_HIP(hipGetLastError());
+    } else if (n) {
+        hipLaunchKernelGGL(k_coarse_hist, grid, dim3(1024), 0, s, keys, gp.kr, pa.fb, pa.NBc, pa.chunk, pa.nch, counts,
+                           wmaj);
+        PNP_HIP(hipGetLastError());
+    }
+    if (wmaj <= 1) PNP_HIP(hipMemsetAsync(counts + ncount, 0, 4, s));
+    scan_u32(counts, ncount + 1, gb.scan_tmp, s);  // counts[ncount] = total
+    return keys;
+}
+
+// the group's entries sorted by bucket into gb.sorted, the bucket starts in gb.offsets
+static void sort_group(MsmWork &wk, MsmGroup &gb, const GroupPlan &gp, const MsmCfg &g, const uint64_t *const *sc,
+                       int B, bool folded, hipStream_t s) {
     const int nv = gp.nv;
     const uint64_t n = gp.kr.n, WB = (uint64_t)nv * g.NB;
-    // points per coarse-pass workgroup: ~512 workgroups in all, >= 1024 points each
-    const int nch0 = std::max(1, 512 / std::max(nv, 1));
-    const uint64_t chunk = std::max<uint64_t>(1024, (n + nch0 - 1) / nch0);
-    const int nch = (int)((n + chunk - 1) / chunk);
-    const int cb = std::min(SORT_CB, g.c - 1), fb = g.c - 1 - cb, NBc = 1 << cb;
-    if (fb > SORT_FB_MAX) {
+    const PassA pa(n, nv, g.c);
+    if (!pa.sortable()) {
         set_error("msm: window of %d bits exceeds the sort's %d", g.c, SORT_CB + SORT_FB_MAX + 1);
         throw Error(PNP_E_ARG);
     }
-    const uint64_t nbins = (uint64_t)nv * NBc;
+    const uint64_t nbins = (uint64_t)nv * pa.NBc, ncount = nbins * pa.nch;
     const uint64_t nent = (uint64_t)nv * gp.kr.rows * n;  // upper bound (zero digits drop out)
-    auto need = [](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
-    need(gb.counts, (nbins * nch + 1) * 4);
-    need(gb.offsets, (WB + 1) * 4);
-    need(gb.ent, nent * 4 + 4);
-    need(gb.fkey, nent * 2 + 8);
-    need(gb.sorted, nent * 4 + 4);
-    uint32_t *counts = static_cast<uint32_t *>(gb.counts.p);
-    uint32_t *bstart = static_cast<uint32_t *>(gb.offsets.p);
-    dim3 grid((uint32_t)nch, (uint32_t)nv);
-    if (scalars) {
-        ScalarPtrs sp{};
-        for (int v = 0; v < nv; v++) sp.p[v] = scalars[v];
-        hipLaunchKernelGGL(k_digits_hist, grid, dim3(1024), 0, s, sp, n, g.c, g.W, g.top_sh, fb, NBc, chunk, nch,
-                           const_cast<uint32_t *>(keys), counts, 1);
-    } else {
-        hipLaunchKernelGGL(k_coarse_hist, grid, dim3(1024), 0, s, keys, gp.kr, fb, NBc, chunk, nch, counts);
-    }
-    PNP_HIP(hipGetLastError());
-    const uint64_t ncount = nbins * nch;
-    PNP_HIP(hipMemsetAsync(counts + ncount, 0, 4, s));
-    scan_u32(counts, ncount + 1, gb.scan_tmp, s);  // counts[ncount] = total
-    uint32_t *ent = static_cast<uint32_t *>(gb.ent.p);
+    gb.offsets.reserve((WB + 1) * 4);
+    gb.ent.reserve(nent * 4 + 4);
+    gb.fkey.reserve(nent * 2 + 8);
+    gb.sorted.reserve(nent * 4 + 4);
+    const uint32_t *keys = pass_a_count(wk, gb, pa, gp, g, sc, B, folded, 1, s);
+    uint32_t *counts = gb.counts.u32(), *bstart = gb.offsets.u32(), *ent = gb.ent.u32();
     uint16_t *fk = static_cast<uint16_t *>(gb.fkey.p);
-    hipLaunchKernelGGL(k_coarse_scatter, grid, dim3(1024), 0, s, keys, gp.kr, fb, NBc, chunk, nch,
-                       counts, ent, fk);
+    hipLaunchKernelGGL(k_coarse_scatter, dim3((uint32_t)pa.nch, (uint32_t)nv), dim3(1024), 0, s, keys, gp.kr, pa.fb,
+                       pa.NBc, pa.chunk, pa.nch, counts, ent, fk);
     PNP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fine_sort, dim3((uint32_t)nbins), dim3(1024), 0, s, ent, fk, counts, nch, fb,
-                       bstart, static_cast<uint32_t *>(gb.sorted.p));
+    hipLaunchKernelGGL(k_fine_sort, dim3((uint32_t)nbins), dim3(1024), 0, s, ent, fk, counts, pa.nch, pa.fb,
+                       bstart, gb.sorted.u32());
     PNP_HIP(hipGetLastError());
     PNP_HIP(hipMemcpyAsync(bstart + WB, counts + ncount, 4, hipMemcpyDeviceToDevice, s));
 }
@@ -1306,6 +1356,12 @@ static uint32_t acc_segment(uint64_t nent, bool folded) {
     // of the additions)
     return (uint32_t)std::max<uint64_t>(16, (per + rounds - 1) / rounds);
 }
+// balanced accumulate: S entries per lane, S >= 64 or ~2^20 lanes (every
+// bucket piece beyond the first costs an addition in msm_merge_pieces)
+static AccLayout acc_layout(uint64_t WB, uint64_t nent, bool folded) {
+    const uint32_t S = acc_segment(nent, folded);
+    return AccLayout{WB, (nent + S - 1) / S, S, (uint32_t)(nent / std::max<uint64_t>(WB, 1) / S + 1)};
+}
 
 // buckets of the group (XYZZ, R384) into gb.buckets
 // nent: entries (upper bound) in the sorted list; alg_bytes: SURVEY 8(d)
@@ -1317,53 +1373,42 @@ static void accumulate_group(MsmWork &wk, MsmGroup &gb, const GroupPlan &gp, con
     const uint64_t n = gp.kr.n, WB = (uint64_t)nv * g.NB;
     if (!nent) nent = (uint64_t)nv * gp.kr.rows * n;
     if (alg_bytes == 0) alg_bytes = (double)n * 128.0 * nv * gp.kr.rows / g.W;
-    auto need = [](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
-    need(gb.buckets, (WB * 24 + WB * 72 + 64) * 8);  // buckets + reduction tree scratch
-    const uint32_t *bstart = static_cast<const uint32_t *>(gb.offsets.p);
-    const uint32_t *sorted = static_cast<const uint32_t *>(gb.sorted.p);
-    uint64_t *bk = gb.buckets.u64();
+    const AccLayout L = acc_layout(WB, gb.acc_nent = nent, table != nullptr);
+    gb.buckets.reserve(L.buckets_bytes());
+    const uint32_t *bstart = gb.offsets.u32(), *sorted = gb.sorted.u32();
     hipEvent_t ev0 = nullptr;
     if (wk.timer) wk.timer->begin("msm_accumulate", s, ev0);
-    // balanced accumulate: S entries per thread, S >= 64 or ~2^20 lanes (every
-    // bucket piece beyond the first costs an addition in msm_merge_pieces)
-    const uint32_t S = acc_segment(nent, table != nullptr);
-    const uint64_t nthr = (nent + S - 1) / S;
     if (table) {
         // raw radix-2^29 pieces: buckets inside one segment, then heads, tails
-        need(gb.seg, (WB + 2 * nthr) * 224 + nthr * 4 + (nthr + 1) * 4);
-        uint32_t *bk29 = static_cast<uint32_t *>(gb.seg.p);
-        uint32_t *head = bk29 + 56 * WB, *tail = head + 56 * nthr, *tailb = tail + 56 * nthr;
-        uint32_t *tlist = tailb + nthr;  // [0] count, then the lanes with a tail
+        gb.seg.reserve(L.seg_bytes());
+        uint32_t *bk29 = gb.seg.u32(), *head = L.head(gb.seg), *tail = L.tail(gb.seg), *tailb = L.tailb(gb.seg);
+        uint32_t *tlist = L.tlist(gb.seg);
         PNP_HIP(hipMemsetAsync(tlist, 0, 4, s));
-        need(gb.redo, nthr * 4 + 16);
-        uint32_t *nredo = static_cast<uint32_t *>(gb.redo.p), *redo = nredo + 4;
+        gb.redo.reserve(L.redo_bytes());
+        uint32_t *nredo = gb.redo.u32(), *redo = L.redo_lanes(gb.redo);
         PNP_HIP(hipMemsetAsync(nredo, 0, 4, s));
         const uint32_t *t29 = reinterpret_cast<const uint32_t *>(table);
-        const uint32_t blocks = (uint32_t)((nthr + 255) / 256);
-        hipLaunchKernelGGL(k_accumulate29, dim3(blocks), dim3(256), 0, s, t29, sorted, bstart, WB, S, bk29,
+        const uint32_t blocks = (uint32_t)((L.nthr + 255) / 256);
+        hipLaunchKernelGGL(k_accumulate29, dim3(blocks), dim3(256), 0, s, t29, sorted, bstart, WB, L.S, bk29,
                            head, tail, tailb, redo, nredo, tlist);
         PNP_HIP(hipGetLastError());
         // equal / opposite points or infinity inside a piece: exact recomputation
         // of the flagged lanes (the count stays on the device: no host sync)
-        hipLaunchKernelGGL(k_accumulate_redo, dim3((uint32_t)std::min<uint64_t>((nthr + 63) / 64, 1024)), dim3(64), 0, s, t29,
-                           sorted, bstart, WB, S, bk29, head, tail, redo, nredo);
+        hipLaunchKernelGGL(k_accumulate_redo, dim3((uint32_t)std::min<uint64_t>((L.nthr + 63) / 64, 1024)), dim3(64), 0,
+                           s, t29, sorted, bstart, WB, L.S, bk29, head, tail, redo, nredo);
         PNP_HIP(hipGetLastError());
         // split buckets into bk29 (in place, F29; empty ones stay unwritten), reduced by msm_reduce29
-        need(gb.exc, 16);
+        gb.exc.reserve(L.exc_bytes());
         PNP_HIP(hipMemsetAsync(gb.exc.p, 0, 4, s));
-        gb.S = S;
-        gb.pieces = (uint32_t)(nent / WB / S + 1);
-        gb.nthr = nthr;
-        need(gb.heavy, (WB + 1) * 4);
-        msm_merge_pieces29(bstart, WB, S, nthr, tailb, tlist, bk29, head, tail, static_cast<uint32_t *>(gb.exc.p),
-                           static_cast<uint32_t *>(gb.heavy.p), s);
+        gb.heavy.reserve(L.heavy_bytes());
+        msm_merge_pieces29(bstart, WB, L.S, L.nthr, tailb, tlist, bk29, head, tail, gb.exc.u32(), gb.heavy.u32(), s);
     } else {
-        need(gb.seg, nthr * 2 * 24 * 8);
-        uint64_t *head = gb.seg.u64(), *tail = head + nthr * 24;
-        hipLaunchKernelGGL(k_accumulate_flat, dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, s, pts,
-                           sorted, bstart, 1, WB, S, bk, head, tail);
+        gb.seg.reserve(L.nthr * 2 * 24 * 8);
+        uint64_t *bk = gb.buckets.u64(), *head = gb.seg.u64(), *tail = head + L.nthr * 24;
+        hipLaunchKernelGGL(k_accumulate_flat, dim3((uint32_t)((L.nthr + 255) / 256)), dim3(256), 0, s, pts,
+                           sorted, bstart, 1, WB, L.S, bk, head, tail);
         PNP_HIP(hipGetLastError());
-        msm_merge_pieces(bstart, 1, WB, S, (uint32_t)(nent / WB / S + 1), head, tail, bk, s);
+        msm_merge_pieces(bstart, 1, WB, L.S, L.pieces, head, tail, bk, s);
     }
     // algorithmic bytes: each point (96 B) and scalar (32 B)
     // once per window sweep
@@ -1372,9 +1417,9 @@ static void accumulate_group(MsmWork &wk, MsmGroup &gb, const GroupPlan &gp, con
         // the dense bound nv x rows x n (zero digits drop out of the real count)
         wk.timer->credit("msm_entries_dense", (double)nent);
         if (table) {  // the real work, counted on the device (k_count_pieces)
-            need(gb.wctr, 8 * (1 + WCTR_SLOTS));
-            PNP_HIP(hipMemsetAsync(gb.wctr.p, 0, 8 * (1 + WCTR_SLOTS), s));
-            hipLaunchKernelGGL(k_count_pieces, dim3((uint32_t)((WB + 1023) / 1024)), dim3(1024), 0, s, bstart, WB, S,
+            gb.wctr.reserve(L.wctr_bytes());
+            PNP_HIP(hipMemsetAsync(gb.wctr.p, 0, L.wctr_bytes(), s));
+            hipLaunchKernelGGL(k_count_pieces, dim3((uint32_t)((WB + 1023) / 1024)), dim3(1024), 0, s, bstart, WB, L.S,
                                static_cast<unsigned long long *>(gb.wctr.p));
             PNP_HIP(hipGetLastError());
             gb.wctr_live = true;
@@ -1382,115 +1427,87 @@ static void accumulate_group(MsmWork &wk, MsmGroup &gb, const GroupPlan &gp, con
     }
 }
 
-// queue the D2H copy of a timed launch's work counters (before the caller's
-// stream synchronisation) / credit them to the timer after it
-static void wctr_fetch(MsmGroup &gb, hipStream_t s) {
-    if (gb.wctr_live) PNP_HIP(hipMemcpyAsync(gb.wctr_h, gb.wctr.p, 8 * (1 + WCTR_SLOTS), hipMemcpyDeviceToHost, s));
-}
-static void wctr_credit(MsmWork &wk, MsmGroup &gb) {
-    if (!gb.wctr_live) return;
-    gb.wctr_live = false;
-    if (!wk.timer) return;
-    unsigned long long pieces = 0;
-    for (int k = 1; k <= WCTR_SLOTS; k++) pieces += gb.wctr_h[k];
-    wk.timer->credit("msm_entries", (double)gb.wctr_h[0]);
-    wk.timer->credit("msm_madds", (double)(gb.wctr_h[0] - pieces));
-}
-
+// nv results (weighted sums T, XYZZ R384) of the last accumulation, followed
+// by the nv plain bucket sums
 static const uint64_t *reduce_group(MsmGroup &gb, const GroupPlan &gp, const MsmCfg &g, hipStream_t s,
                                     bool folded) {
-    const uint64_t WB = (uint64_t)gp.nv * g.NB;
-    uint64_t *bk = gb.buckets.u64();
     if (folded)  // radix-2^29 buckets in gb.seg, the tree in gb.buckets
-        return msm_reduce29(static_cast<const uint32_t *>(gb.seg.p), static_cast<const uint32_t *>(gb.offsets.p),
-                            (uint64_t)gp.nv, g.NB,
-                            reinterpret_cast<uint32_t *>(bk), static_cast<uint32_t *>(gb.exc.p), s);
-    return msm_reduce(bk, (uint64_t)gp.nv, g.NB, bk + WB * 24, s);
+        return msm_reduce29(gb.seg.u32(), gb.offsets.u32(), (uint64_t)gp.nv, g.NB, gb.buckets.u32(), gb.exc.u32(), s);
+    const uint64_t nv = gp.nv;
+    return msm_reduce(gb.buckets.u64(), nv, g.NB, acc_layout(nv * g.NB, gb.acc_nent, false).tree(gb.buckets), s);
 }
 
 // the exact 32-bit merge + reduction of a folded group whose F29 pass met an
 // exceptional addition (equal / opposite operands: repeated bases, crafted
 // scalars); same inputs, left untouched by the F29 pass
 static const uint64_t *reduce_group_exact(MsmGroup &gb, const GroupPlan &gp, const MsmCfg &g, hipStream_t s) {
-    const uint64_t WB = (uint64_t)gp.nv * g.NB;
+    const AccLayout L = acc_layout((uint64_t)gp.nv * g.NB, gb.acc_nent, true);
     uint64_t *bk = gb.buckets.u64();
-    const uint32_t *bk29 = static_cast<const uint32_t *>(gb.seg.p);
-    const uint32_t *head = bk29 + 56 * WB, *tail = head + 56 * gb.nthr;
-    msm_merge_pieces29_exact(static_cast<const uint32_t *>(gb.offsets.p), WB, gb.S, gb.pieces, bk29, head, tail,
-                             bk, s);
-    return msm_reduce(bk, (uint64_t)gp.nv, g.NB, bk + WB * 24, s);
+    msm_merge_pieces29_exact(gb.offsets.u32(), L.WB, L.S, L.pieces, gb.seg.u32(), L.head(gb.seg), L.tail(gb.seg), bk,
+                             s);
+    return msm_reduce(bk, (uint64_t)gp.nv, g.NB, L.tree(gb.buckets), s);
+}
+
+// The end of a group, two steps around the caller's ONE stream synchronisation.
+// group_fetch queues the copies to the host: the results, a folded group's
+// exception word and redo count, `extra`'s (the slot exchange's flags and
+// destination counts, on the same synchronisation), a timed run's work counters
+static void group_fetch(MsmGroup &gb, const uint64_t *res, std::vector<uint64_t> &out, bool folded, hipStream_t s,
+                        const std::function<void()> &extra = nullptr) {
+    gb.exc_h = gb.nredo_h = 0;
+    PNP_HIP(hipMemcpyAsync(out.data(), res, out.size() * 8, hipMemcpyDeviceToHost, s));
+    if (folded) {
+        PNP_HIP(hipMemcpyAsync(&gb.exc_h, gb.exc.p, 4, hipMemcpyDeviceToHost, s));
+        PNP_HIP(hipMemcpyAsync(&gb.nredo_h, gb.redo.p, 4, hipMemcpyDeviceToHost, s));
+    }
+    if (extra) extra();
+    if (gb.wctr_live) PNP_HIP(hipMemcpyAsync(gb.wctr_h, gb.wctr.p, sizeof gb.wctr_h, hipMemcpyDeviceToHost, s));
+}
+// group_finish, after it: credits the counters, redoes the group exactly on an
+// exception (a second copy and synchronisation), collects the timer's events
+static void group_finish(MsmWork &wk, MsmGroup &gb, const GroupPlan &gp, const MsmCfg &g, std::vector<uint64_t> &out,
+                         hipStream_t s) {
+    if (gb.wctr_live && wk.timer) {
+        unsigned long long pieces = 0;
+        for (int k = 1; k <= WCTR_SLOTS; k++) pieces += gb.wctr_h[k];
+        wk.timer->credit("msm_entries", (double)gb.wctr_h[0]);
+        wk.timer->credit("msm_madds", (double)(gb.wctr_h[0] - pieces));
+    }
+    gb.wctr_live = false;
+    // accumulation lanes recomputed exactly (a degenerate step in a piece)
+    if (wk.timer) wk.timer->credit("msm_redo_lanes", (double)gb.nredo_h);
+    if (gb.exc_h) {
+        if (wk.timer) wk.timer->credit("msm_exact_fallback", 1);
+        PNP_HIP(hipMemcpyAsync(out.data(), reduce_group_exact(gb, gp, g, s), out.size() * 8, hipMemcpyDeviceToHost, s));
+        PNP_HIP(hipStreamSynchronize(s));
+    }
+    if (wk.timer) wk.timer->collect();
 }
 
 // B independent MSMs over the same n points, on this GPU only; the B results
 // (XYZZ) land in h_xyzz.  Per-window layout: the B*W windows are "virtual
-// windows" of NB buckets each.  Folded layout (table != nullptr): virtual
+// windows" of NB buckets each.  Folded layout (tv.table != nullptr): virtual
 // window b = MSM b with the W key rows of its windows, one bucket set.
 // One group on one stream: the sort cannot be hidden under the accumulation
 // on this chip (the two-stream pipeline).
-// n_table / id_base: a folded table built over n_table points of which this
-// call's points are [id_base, id_base + n) (bucket-range mode keeps the full
-// table; a point-range batch then indexes into it); 0 = the table is this range
-static void msm_local_batch(MsmWork &wk, const uint64_t *d_points, const uint64_t *const *d_scalars,
-                            int B, uint64_t n, uint64_t *h_xyzz, hipStream_t s,
-                            const uint64_t *table, uint64_t n_table = 0, uint64_t id_base = 0,
-                            const uint64_t *seg_off = nullptr, int cfg_c = 0) {
+static void msm_local_batch(MsmWork &wk, const uint64_t *d_points, const uint64_t *const *d_scalars, int B,
+                            uint64_t n, uint64_t *h_xyzz, hipStream_t s, const TableView &tv) {
     if (n == 0 || B == 0) {
         for (int b = 0; b < B; b++) put_xyzz(Xyzz::inf(), h_xyzz + 24 * b);
         return;
     }
-    const bool folded = table != nullptr;
-    if (!n_table) n_table = n;
-    const MsmCfg g = msm_cfg(n_table, folded ? (cfg_c ? cfg_c : wk.fold_c) : 0, folded);
-    auto need = [](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
-    need(wk.digits, (uint64_t)g.W * B * n * 4);
-    uint32_t *keys = static_cast<uint32_t *>(wk.digits.p);
-    // the fused pass makes the keys of the standard folded group
-    const bool fuse = folded && B <= ScalarPtrs::MAX;
-    if (!fuse) {
-        for (int b = 0; b < B; b++) {
-            hipLaunchKernelGGL(k_digits, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d_scalars[b], n,
-                               g.c, g.W, g.top_sh, keys + (uint64_t)b * g.W * n);
-            PNP_HIP(hipGetLastError());
-        }
-    }
-    GroupPlan gp;
-    gp.kr.n = n;
-    if (!folded) {
-        gp.kr.vstride = 1, gp.kr.off = 0, gp.kr.rows = 1, gp.kr.id_row0 = 0, gp.kr.id_mul = 0;
-        gp.nv = B * g.W;
-    } else {
-        gp.kr.vstride = g.W, gp.kr.off = 0, gp.kr.rows = g.W, gp.kr.id_row0 = 0, gp.kr.id_mul = n_table;
-        gp.kr.id_base = id_base;
-        gp.nv = B;
-    }
-    if (seg_off) {  // MSM v starts at seg_off[v]
-        gp.kr.nseg = gp.nv;
-        for (int v = 0; v < gp.nv; v++) gp.kr.seg_off[v] = seg_off[v];
-    }
-    const uint64_t *pts = folded ? table : d_points;
+    const bool folded = tv.table != nullptr;
+    const MsmCfg g = tv.cfg(wk);
+    // (per-window: one key row per virtual window, the entry is the point index)
+    const GroupPlan gp =
+        folded ? GroupPlan{folded_rows(n, B, g, tv), B} : GroupPlan{KeyRows{n, 1, 0, 1, 0, 0}, B * g.W};
     MsmGroup &gb = wk.grp;
-    sort_group(wk, gb, keys, gp, g, s, fuse ? d_scalars : nullptr);
-    accumulate_group(wk, gb, gp, g, pts, table, s);
-    const uint64_t *res = reduce_group(gb, gp, g, s, folded);
+    sort_group(wk, gb, gp, g, d_scalars, B, folded, s);
+    accumulate_group(wk, gb, gp, g, d_points, tv.table, s);
     std::vector<uint64_t> win((size_t)gp.nv * 24);
-    uint32_t exc = 0, nredo = 0;
-    PNP_HIP(hipMemcpyAsync(win.data(), res, win.size() * 8, hipMemcpyDeviceToHost, s));
-    if (folded) {
-        PNP_HIP(hipMemcpyAsync(&exc, gb.exc.p, 4, hipMemcpyDeviceToHost, s));
-        PNP_HIP(hipMemcpyAsync(&nredo, gb.redo.p, 4, hipMemcpyDeviceToHost, s));
-        wctr_fetch(gb, s);
-    }
+    group_fetch(gb, reduce_group(gb, gp, g, s, folded), win, folded, s);
     PNP_HIP(hipStreamSynchronize(s));
-    wctr_credit(wk, gb);
-    // accumulation lanes recomputed exactly (a degenerate step in a piece)
-    if (wk.timer) wk.timer->credit("msm_redo_lanes", (double)nredo);
-    if (exc) {
-        if (wk.timer) wk.timer->credit("msm_exact_fallback", 1);
-        res = reduce_group_exact(gb, gp, g, s);
-        PNP_HIP(hipMemcpyAsync(win.data(), res, win.size() * 8, hipMemcpyDeviceToHost, s));
-        PNP_HIP(hipStreamSynchronize(s));
-    }
-    if (wk.timer) wk.timer->collect();
+    group_finish(wk, gb, gp, g, win, s);
     if (folded) {  // virtual window b is MSM b
         std::copy(win.begin(), win.end(), h_xyzz);
     } else {
@@ -1562,179 +1579,105 @@ static Xyzz mul_small(const Xyzz &p, uint64_t k) {
 // with 512 coarse bins, whose top log2(W) bits are the owning rank, in
 // destination-major order (cidx), writing 8-byte records (entry | fine key <<
 // 32) straight into the send buffer: destination d's part is one run.  After
-// the all-to-all (bin counts first, then the records) every rank sorts its own
-// bins from the W received runs (k_fine_sort_runs), then accumulates, merges
-// and reduces only its NB/W buckets per MSM: 1/W of the bucket tail that the
-// point-range scheme repeats on every rank.  Its share of MSM b is
-// T_b + lo S_b (T: the local tree's weighted sum, S: the plain bucket sum,
-// lo = r NB/W: the weight offset of its buckets).  Returns false (nothing
-// exchanged; every rank reaches the same verdict from the all-gathered
-// counts) when the records would overflow the exchange buffers: the caller
-// then takes point ranges.
-static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint64_t n_full, uint64_t p0,
-                             uint64_t p1, uint64_t *part, hipStream_t s, const uint64_t *table,
-                             const uint64_t *seg_off = nullptr, int cfg_c = 0) {
+// the all-to-all (fixed slots, bucket_slots, or bin counts first and then the
+// records, bucket_variable) every rank sorts its own bins from the W received
+// runs (k_fine_sort_runs), then accumulates, merges and reduces only its NB/W
+// buckets per MSM: 1/W of the bucket tail that the point-range scheme repeats
+// on every rank.  Its share of MSM b is T_b + lo S_b (T: the local tree's
+// weighted sum, S: the plain bucket sum, lo = r NB/W: the weight offset of its
+// buckets).  What msm_bucket_batch's front hands to either exchange:
+struct BucketBatch {
+    int B;
+    const uint64_t *table;
+    MsmCfg g, gl;  // the table's windows; the same with this rank's NB / W buckets
+    GroupPlan gp;  // this rank's n points, B bucket sets
+    PassA pa;
+    const uint32_t *keys;  // (the scanned counts, destination-major, are in MsmGroup::counts)
+    std::tuple<uint32_t, int, uint64_t> key;  // of MsmWork::slot_cap
+    dim3 grid() const { return dim3((uint32_t)pa.nch, (uint32_t)B); }
+};
+
+// Fixed slots of `cap` records per (source, destination): no host round trip
+// before the accumulation.  false: some rank overflowed some slot (every rank
+// saw its flag); the caller redoes the batch with bucket_variable, which
+// raises the capacity
+static bool bucket_slots(MsmWork &wk, const BucketBatch &bb, uint64_t cap, std::vector<uint64_t> &ts, hipStream_t s) {
     const int W = wk.world;
-    // Bucket ranges pay from 4 ranks on (solo-rank times per proof at n = 2^22,
-    // points vs buckets: 2 ranks 91.1 vs 94.0 ms, 4 ranks 56.0 vs 55.3, 8 ranks
-    // 37.5 vs 34.6, profiles/r03_solo): below that the extra exchange and sort
-    // cost more than the halved bucket tail saves.  PNP_MSM_BUCKETS_MIN_WORLD
-    // moves the threshold (tests cover 2 ranks with it).
-    static const int min_world = [] {
-        const char *e = getenv("PNP_MSM_BUCKETS_MIN_WORLD");
-        return e ? atoi(e) : 4;
-    }();
-    if (W < min_world) return false;
-    const MsmCfg g = msm_cfg(n_full, cfg_c ? cfg_c : wk.fold_c, true);
-    int lgW = 0;
-    while ((1 << lgW) < W) lgW++;
-    const int cbits = std::min(SORT_CB, g.c - 1);  // coarse bits of the whole bucket index
-    if ((1 << lgW) != W || lgW >= cbits || g.c - 1 - cbits > SORT_FB_MAX) return false;
-    const int fb = g.c - 1 - cbits, NBc = 1 << cbits, nbl = NBc / W;  // nbl coarse bins per rank
-    const uint64_t NBloc = (uint64_t)g.NB / W, n = p1 - p0;
-    if (NBloc < 32) return false;
-    auto need = [](DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); };
+    const PassA &pa = bb.pa;
+    // coarse bins per destination; this rank's buckets
+    const uint64_t per_d = (uint64_t)bb.B * (pa.NBc / W), WB = (uint64_t)bb.B * bb.gl.NB;
+    const uint32_t hdr = slot_hdr_recs((uint32_t)per_d);                  // records of a slot's header
+    const uint64_t slot_recs = hdr + cap;
     MsmGroup &gb = wk.grp;
-    // 1. digits of this rank's points
-    need(wk.digits, (uint64_t)g.W * B * std::max<uint64_t>(n, 1) * 4);
-    uint32_t *keys = static_cast<uint32_t *>(wk.digits.p);
-    const bool fuse = B <= ScalarPtrs::MAX;  // digits made by the histogram pass
-    for (int b = 0; b < B && n && !fuse; b++) {
-        hipLaunchKernelGGL(k_digits, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sc[b], n, g.c, g.W,
-                           g.top_sh, keys + (uint64_t)b * g.W * n);
+    uint32_t *counts = gb.counts.u32();
+    // u32 layout of slot_dev: runs (2 per_d W) | out0 (per_d + 1) | flags (2) | dest counts (W)
+    const uint64_t nruns = 2 * per_d * W;
+    wk.slot_dev.reserve((nruns + per_d + 1 + 2 + W) * 4);
+    uint32_t *rt = wk.slot_dev.u32(), *o0 = rt + nruns, *flags = o0 + per_d + 1, *dcnt = flags + 2;
+    hipLaunchKernelGGL(k_slot_header, dim3((uint32_t)W), dim3(256), 0, s, counts, (uint32_t)per_d, pa.nch, W,
+                       (uint32_t)slot_recs, (uint32_t)cap, wk.v_send, dcnt);
+    PNP_HIP(hipGetLastError());
+    if (bb.gp.kr.n) {
+        hipLaunchKernelGGL(k_coarse_scatter, bb.grid(), dim3(1024), 0, s, bb.keys, bb.gp.kr, pa.fb, pa.NBc, pa.chunk,
+                           pa.nch, counts, nullptr, nullptr, W, wk.v_send, (uint32_t)slot_recs, hdr, (uint32_t)cap);
         PNP_HIP(hipGetLastError());
     }
-    // 2. pass A, destination-major (chunks as sort_group: ~512 workgroups)
-    KeyRows kr;
-    kr.n = n, kr.vstride = g.W, kr.off = 0, kr.rows = g.W, kr.id_row0 = 0, kr.id_mul = n_full, kr.id_base = p0;
-    if (seg_off) {
-        kr.nseg = B;
-        for (int b = 0; b < B; b++) kr.seg_off[b] = seg_off[b];
+    ex_fence(wk, s);
+    std::vector<uint64_t> eq(W, slot_recs * 8);
+    if (int rc = wk.alltoallv(wk.v_user, eq.data(), eq.data())) {
+        set_error("msm bucket shard: slot all-to-all failed (%d)", rc);
+        throw Error(PNP_E_DEVICE);
     }
-    const int nch0 = std::max(1, 512 / B);
-    const uint64_t chunk = std::max<uint64_t>(1024, (n + nch0 - 1) / nch0);
-    const int nch = (int)std::max<uint64_t>(1, (n + chunk - 1) / chunk);
-    const uint64_t ncount = (uint64_t)B * NBc * nch;
-    need(gb.counts, (ncount + 1) * 4);
-    uint32_t *counts = static_cast<uint32_t *>(gb.counts.p);
-    PNP_HIP(hipMemsetAsync(counts, 0, (ncount + 1) * 4, s));
-    const dim3 grid((uint32_t)nch, (uint32_t)B);
-    if (n && fuse) {
-        ScalarPtrs sp{};
-        for (int b = 0; b < B; b++) sp.p[b] = sc[b];
-        hipLaunchKernelGGL(k_digits_hist, grid, dim3(1024), 0, s, sp, n, g.c, g.W, g.top_sh, fb, NBc, chunk, nch, keys,
-                           counts, W);
-        PNP_HIP(hipGetLastError());
-    } else if (n) {
-        hipLaunchKernelGGL(k_coarse_hist, grid, dim3(1024), 0, s, keys, kr, fb, NBc, chunk, nch, counts, W);
-        PNP_HIP(hipGetLastError());
-    }
-    scan_u32(counts, ncount + 1, gb.scan_tmp, s);
-    const uint64_t per_d = (uint64_t)B * nbl;
-    const uint64_t WB = (uint64_t)B * NBloc;
-    const uint64_t lo_w = (uint64_t)wk.rank * NBloc;  // weight offset of this rank's buckets
-    // this batch's slot capacity (the same key, and so the same capacity, on
-    // every rank: the ranks run the same batches in the same order)
-    static const bool slots_on = [] {
-        const char *e = getenv("PNP_MSM_SLOTS");
-        return !(e && atoi(e) == 0);
-    }();
-    if (wk.slot_cap.size() > 1024) wk.slot_cap.clear();  // (operator-API batches never repeat a key)
-    const auto key = std::make_tuple(wk.batch_seq++, B, n_full);
-    const uint32_t hdr = slot_hdr_recs((uint32_t)per_d);
-    auto cap_it = wk.slot_cap.find(key);
-    if (slots_on && W <= SLOT_W_MAX && cap_it != wk.slot_cap.end()) {
-        // ---- fixed slots: no host round trip before the accumulation
-        // (PNP_TEST_SLOT_CAP: a smaller capacity, to exercise the overflow path)
-        static const uint64_t test_cap = [] {
-            const char *e = getenv("PNP_TEST_SLOT_CAP");
-            return e ? strtoull(e, nullptr, 0) : 0ULL;
-        }();
-        const uint64_t cap = test_cap ? std::min(test_cap, cap_it->second) : cap_it->second;
-        const uint64_t slot_recs = hdr + cap;
-        // u32 layout of slot_dev: runs (2 per_d W) | out0 (per_d + 1) | flags (2) | dest counts (W)
-        const uint64_t nruns = 2 * per_d * W;
-        need(wk.slot_dev, (nruns + per_d + 1 + 2 + W) * 4);
-        uint32_t *rt = static_cast<uint32_t *>(wk.slot_dev.p), *o0 = rt + nruns, *flags = o0 + per_d + 1,
-                 *dcnt = flags + 2;
-        hipLaunchKernelGGL(k_slot_header, dim3((uint32_t)W), dim3(256), 0, s, counts, (uint32_t)per_d, nch, W,
-                           (uint32_t)slot_recs, (uint32_t)cap, wk.v_send, dcnt);
-        PNP_HIP(hipGetLastError());
-        if (n) {
-            hipLaunchKernelGGL(k_coarse_scatter, grid, dim3(1024), 0, s, keys, kr, fb, NBc, chunk, nch, counts,
-                               nullptr, nullptr, W, wk.v_send, (uint32_t)slot_recs, hdr, (uint32_t)cap);
-            PNP_HIP(hipGetLastError());
-        }
-        ex_fence(wk, s);
-        std::vector<uint64_t> eq(W, slot_recs * 8);
-        if (int rc = wk.alltoallv(wk.v_user, eq.data(), eq.data())) {
-            set_error("msm bucket shard: slot all-to-all failed (%d)", rc);
-            throw Error(PNP_E_DEVICE);
-        }
-        need(gb.offsets, (WB + 1) * 4);
-        need(gb.sorted, W * cap * 4 + 4);
-        uint32_t *bstart = static_cast<uint32_t *>(gb.offsets.p);
-        hipLaunchKernelGGL(k_slot_runs, dim3(1), dim3(1024), 0, s, wk.v_recv, W, (uint32_t)slot_recs, hdr,
-                           (uint32_t)per_d, (uint32_t)cap, reinterpret_cast<uint2 *>(rt), o0, bstart + WB, flags);
-        PNP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_fine_sort_runs, dim3((uint32_t)per_d), dim3(1024), 0, s, wk.v_recv,
-                           reinterpret_cast<const uint2 *>(rt), W, o0, fb, bstart,
-                           static_cast<uint32_t *>(gb.sorted.p));
-        PNP_HIP(hipGetLastError());
-        MsmCfg gl = g;
-        gl.NB = (int)NBloc;
-        GroupPlan gp;
-        gp.kr = kr;
-        gp.nv = B;
-        // (the record count stays on the device: W cap bounds the lanes, the
-        // kernels read the true total from bstart[WB])
-        accumulate_group(wk, gb, gp, gl, nullptr, table, s, W * cap, (double)W * cap * 128.0 / g.W);
-        const uint64_t *res = reduce_group(gb, gp, gl, s, true);
-        std::vector<uint64_t> ts((size_t)B * 48);
-        uint32_t exc = 0, nredo = 0, fl[2] = {0, 0};
-        std::vector<uint32_t> dc(W);
-        PNP_HIP(hipMemcpyAsync(ts.data(), res, ts.size() * 8, hipMemcpyDeviceToHost, s));
-        PNP_HIP(hipMemcpyAsync(&exc, gb.exc.p, 4, hipMemcpyDeviceToHost, s));
-        PNP_HIP(hipMemcpyAsync(&nredo, gb.redo.p, 4, hipMemcpyDeviceToHost, s));
+    gb.offsets.reserve((WB + 1) * 4);
+    gb.sorted.reserve(W * cap * 4 + 4);
+    uint32_t *bstart = gb.offsets.u32();
+    hipLaunchKernelGGL(k_slot_runs, dim3(1), dim3(1024), 0, s, wk.v_recv, W, (uint32_t)slot_recs, hdr,
+                       (uint32_t)per_d, (uint32_t)cap, reinterpret_cast<uint2 *>(rt), o0, bstart + WB, flags);
+    PNP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_fine_sort_runs, dim3((uint32_t)per_d), dim3(1024), 0, s, wk.v_recv,
+                       reinterpret_cast<const uint2 *>(rt), W, o0, pa.fb, bstart,
+                       gb.sorted.u32());
+    PNP_HIP(hipGetLastError());
+    // (the record count stays on the device: W cap bounds the lanes, the
+    // kernels read the true total from bstart[WB])
+    accumulate_group(wk, gb, bb.gp, bb.gl, nullptr, bb.table, s, W * cap, (double)W * cap * 128.0 / bb.g.W);
+    uint32_t fl[2] = {0, 0};
+    std::vector<uint32_t> dc(W);
+    group_fetch(gb, reduce_group(gb, bb.gp, bb.gl, s, true), ts, true, s, [&] {
         PNP_HIP(hipMemcpyAsync(fl, flags, 8, hipMemcpyDeviceToHost, s));
         PNP_HIP(hipMemcpyAsync(dc.data(), dcnt, 4 * W, hipMemcpyDeviceToHost, s));
-        wctr_fetch(gb, s);
-        PNP_HIP(hipStreamSynchronize(s));
-        wk.slot_runs++;
-        if (fl[0]) {
-            // some rank overflowed some slot (every rank saw its flag): the
-            // variable path below redoes the batch and raises the capacity
-            gb.wctr_live = false;
-            wk.slot_overflows++;
-            if (wk.timer) {
-                wk.timer->credit("msm_slot_overflows", 1);
-                wk.timer->collect();
-            }
-        } else {
-            wctr_credit(wk, gb);
-            if (wk.timer) {
-                wk.timer->credit("msm_slot_batches", 1);
-                wk.timer->credit("msm_redo_lanes", (double)nredo);
-                uint64_t mx = 0, sum = 0;
-                for (uint32_t c : dc) mx = std::max<uint64_t>(mx, c), sum += c;
-                wk.timer->credit("msm_dest_max", (double)mx);
-                wk.timer->credit("msm_dest_sum", (double)sum);
-            }
-            if (exc) {
-                if (wk.timer) wk.timer->credit("msm_exact_fallback", 1);
-                res = reduce_group_exact(gb, gp, gl, s);
-                PNP_HIP(hipMemcpyAsync(ts.data(), res, ts.size() * 8, hipMemcpyDeviceToHost, s));
-                PNP_HIP(hipStreamSynchronize(s));
-            }
-            if (wk.timer) wk.timer->collect();
-            for (int b = 0; b < B; b++) {
-                const Xyzz T = get_xyzz(&ts[24 * (size_t)b]), S = get_xyzz(&ts[24 * ((size_t)B + b)]);
-                put_xyzz(lo_w ? add(T, mul_small(S, lo_w)) : T, part + 24 * (size_t)b);
-            }
-            return true;
+    });
+    PNP_HIP(hipStreamSynchronize(s));
+    wk.slot_runs++;
+    if (fl[0]) {
+        gb.wctr_live = false;  // (the work counters of the dropped run are not credited)
+        wk.slot_overflows++;
+        if (wk.timer) {
+            wk.timer->credit("msm_slot_overflows", 1);
+            wk.timer->collect();
         }
+        return false;
     }
-    // ---- variable sizes: the counts travel first (host round trips)
+    if (wk.timer) {
+        wk.timer->credit("msm_slot_batches", 1);
+        uint64_t mx = 0, sum = 0;
+        for (uint32_t c : dc) mx = std::max<uint64_t>(mx, c), sum += c;
+        wk.timer->credit("msm_dest_max", (double)mx);
+        wk.timer->credit("msm_dest_sum", (double)sum);
+    }
+    group_finish(wk, gb, bb.gp, bb.gl, ts, s);
+    return true;
+}
+
+// Variable sizes: the counts travel first (host round trips).  false
+// (nothing exchanged; every rank reaches the same verdict from the
+// all-gathered counts) when the records would overflow the exchange buffers:
+// the caller then takes point ranges.
+static bool bucket_variable(MsmWork &wk, const BucketBatch &bb, std::vector<uint64_t> &ts, hipStream_t s) {
+    const int W = wk.world, B = bb.B, nch = bb.pa.nch;
+    const uint64_t per_d = (uint64_t)B * (bb.pa.NBc / W), WB = (uint64_t)B * bb.gl.NB, ncount = per_d * W * nch;
+    MsmGroup &gb = wk.grp;
+    uint32_t *counts = gb.counts.u32();
     std::vector<uint32_t> offs(ncount + 1);
     PNP_HIP(hipMemcpyAsync(offs.data(), counts, (ncount + 1) * 4, hipMemcpyDeviceToHost, s));
     PNP_HIP(hipStreamSynchronize(s));
@@ -1743,8 +1686,8 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
     auto bin_off = [&](uint64_t gbin) { return offs[gbin * nch]; };
     std::vector<uint64_t> send_b(W), recv_b(W);
     for (int d = 0; d < W; d++) send_b[d] = 8ULL * (bin_off((d + 1) * per_d) - bin_off(d * per_d));
-    // 3. every rank's totals (one all-gather of W words per rank): the
-    // receive sizes and the common overflow verdict
+    // every rank's totals (one all-gather of W words per rank): the receive
+    // sizes and the common overflow verdict
     const std::vector<uint64_t> all = rank_allgather(wk, s, send_b.data(), W, PNP_EX_TAG_COUNTS);
     auto cnt = [&](int from, int to) { return all[(size_t)from * W + to]; };
     const uint64_t bins_bytes = 4 * per_d * W;  // the bin-count exchange below
@@ -1768,8 +1711,9 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
         uint64_t mx = 0;
         for (uint64_t v : all) mx = std::max<uint64_t>(mx, v / 8);
         const uint64_t cap = ((mx + mx / 32 + 256) + 63) & ~63ULL;
-        if (W <= SLOT_W_MAX && (uint64_t)W * (hdr + cap) * 8 <= wk.v_bytes && cap < (1ULL << 31)) {
-            uint64_t &c = wk.slot_cap[key];
+        const uint64_t slot_recs = slot_hdr_recs((uint32_t)per_d) + cap;
+        if (W <= SLOT_W_MAX && W * slot_recs * 8 <= wk.v_bytes && cap < (1ULL << 31)) {
+            uint64_t &c = wk.slot_cap[bb.key];
             c = std::max(c, cap);
         }
         if (wk.timer) {
@@ -1780,9 +1724,9 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
         }
     }
     for (int r = 0; r < W; r++) recv_b[r] = cnt(r, wk.rank);
-    // 4. bin counts (u32, B nbl per destination), then the records.  `bc`
-    // lives until the stream synchronisation below: in ordered mode nothing
-    // waits for its upload before then
+    // bin counts (u32, B nbl per destination), then the records.  `bc` lives
+    // until the stream synchronisation below: in ordered mode nothing waits
+    // for its upload before then
     std::vector<uint32_t> bc((size_t)per_d * W);
     {
         for (uint64_t gbin = 0; gbin < per_d * W; gbin++) bc[gbin] = bin_off(gbin + 1) - bin_off(gbin);
@@ -1796,9 +1740,9 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
     }
     std::vector<uint32_t> rbc((size_t)per_d * W);  // [source][v][local bin]
     PNP_HIP(hipMemcpyAsync(rbc.data(), wk.v_recv, rbc.size() * 4, hipMemcpyDeviceToHost, s));
-    if (n) {
-        hipLaunchKernelGGL(k_coarse_scatter, grid, dim3(1024), 0, s, keys, kr, fb, NBc, chunk, nch, counts,
-                           nullptr, nullptr, W, wk.v_send);
+    if (bb.gp.kr.n) {
+        hipLaunchKernelGGL(k_coarse_scatter, bb.grid(), dim3(1024), 0, s, bb.keys, bb.gp.kr, bb.pa.fb, bb.pa.NBc,
+                           bb.pa.chunk, nch, counts, nullptr, nullptr, W, wk.v_send);
         PNP_HIP(hipGetLastError());
     }
     PNP_HIP(hipStreamSynchronize(s));
@@ -1806,7 +1750,7 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
         set_error("msm bucket shard: all-to-all failed (%d)", rc);
         throw Error(PNP_E_DEVICE);
     }
-    // 5. the W received runs of every bin (v, local coarse bin) and its output start
+    // the W received runs of every bin (v, local coarse bin) and its output start
     std::vector<uint32_t> runs(2 * per_d * W), out0(per_d + 1);
     {
         uint64_t base = 0;
@@ -1833,44 +1777,78 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
         out0[per_d] = (uint32_t)o;
     }
     const uint64_t R = out0[per_d];
-    need(gb.offsets, (WB + 1) * 4);
-    need(gb.sorted, R * 4 + 4);
-    need(gb.ent, (runs.size() + out0.size()) * 4);  // run table + bin starts (ent is unused on this path)
-    uint32_t *bstart = static_cast<uint32_t *>(gb.offsets.p);
-    uint32_t *rt = static_cast<uint32_t *>(gb.ent.p), *o0 = rt + runs.size();
+    gb.offsets.reserve((WB + 1) * 4);
+    gb.sorted.reserve(R * 4 + 4);
+    gb.ent.reserve((runs.size() + out0.size()) * 4);  // run table + bin starts (ent is unused on this path)
+    uint32_t *bstart = gb.offsets.u32();
+    uint32_t *rt = gb.ent.u32(), *o0 = rt + runs.size();
     PNP_HIP(hipMemcpyAsync(rt, runs.data(), runs.size() * 4, hipMemcpyHostToDevice, s));
     PNP_HIP(hipMemcpyAsync(o0, out0.data(), out0.size() * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_fine_sort_runs, dim3((uint32_t)per_d), dim3(1024), 0, s, wk.v_recv,
-                       reinterpret_cast<const uint2 *>(rt), W, o0, fb, bstart, static_cast<uint32_t *>(gb.sorted.p));
+                       reinterpret_cast<const uint2 *>(rt), W, o0, bb.pa.fb, bstart,
+                       gb.sorted.u32());
     PNP_HIP(hipGetLastError());
     PNP_HIP(hipMemcpyAsync(bstart + WB, o0 + per_d, 4, hipMemcpyDeviceToDevice, s));
-    // 6. accumulate, merge and reduce this rank's buckets
-    MsmCfg gl = g;
-    gl.NB = (int)NBloc;
-    GroupPlan gp;
-    gp.kr = kr;
-    gp.nv = B;
-    std::vector<uint64_t> ts((size_t)B * 48);
+    // accumulate, merge and reduce this rank's buckets
     for (int b = 0; b < 2 * B; b++) put_xyzz(Xyzz::inf(), &ts[24 * (size_t)b]);
     if (R) {
-        accumulate_group(wk, gb, gp, gl, nullptr, table, s, R, (double)R * 128.0 / g.W);
-        const uint64_t *res = reduce_group(gb, gp, gl, s, true);
-        uint32_t exc = 0, nredo = 0;
-        PNP_HIP(hipMemcpyAsync(ts.data(), res, ts.size() * 8, hipMemcpyDeviceToHost, s));
-        PNP_HIP(hipMemcpyAsync(&exc, gb.exc.p, 4, hipMemcpyDeviceToHost, s));
-        PNP_HIP(hipMemcpyAsync(&nredo, gb.redo.p, 4, hipMemcpyDeviceToHost, s));
-        wctr_fetch(gb, s);
+        accumulate_group(wk, gb, bb.gp, bb.gl, nullptr, bb.table, s, R, (double)R * 128.0 / bb.g.W);
+        group_fetch(gb, reduce_group(gb, bb.gp, bb.gl, s, true), ts, true, s);
         PNP_HIP(hipStreamSynchronize(s));
-        wctr_credit(wk, gb);
-        if (wk.timer) wk.timer->credit("msm_redo_lanes", (double)nredo);
-        if (exc) {
-            if (wk.timer) wk.timer->credit("msm_exact_fallback", 1);
-            res = reduce_group_exact(gb, gp, gl, s);
-            PNP_HIP(hipMemcpyAsync(ts.data(), res, ts.size() * 8, hipMemcpyDeviceToHost, s));
-            PNP_HIP(hipStreamSynchronize(s));
-        }
-        if (wk.timer) wk.timer->collect();
+        group_finish(wk, gb, bb.gp, bb.gl, ts, s);
     }
+    return true;
+}
+
+// B folded MSMs over this rank's n points of the full table tv, by bucket
+// ranges.  false: not eligible (nothing launched), or the records would
+// overflow the exchange buffers; the caller then takes point ranges.
+static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint64_t n, uint64_t *part,
+                             hipStream_t s, const TableView &tv) {
+    const int W = wk.world;
+    // Bucket ranges pay from 4 ranks on (solo-rank times per proof at n = 2^22,
+    // points vs buckets: 2 ranks 91.1 vs 94.0 ms, 4 ranks 56.0 vs 55.3, 8 ranks
+    // 37.5 vs 34.6, profiles/r03_solo): below that the extra exchange and sort
+    // cost more than the halved bucket tail saves.  PNP_MSM_BUCKETS_MIN_WORLD
+    // moves the threshold (tests cover 2 ranks with it).
+    static const int min_world = [] {
+        const char *e = getenv("PNP_MSM_BUCKETS_MIN_WORLD");
+        return e ? atoi(e) : 4;
+    }();
+    if (W < min_world) return false;
+    const MsmCfg g = tv.cfg(wk);
+    const PassA pa(n, B, g.c);  // coarse bits of the whole bucket index
+    int lgW = 0;
+    while ((1 << lgW) < W) lgW++;
+    if ((1 << lgW) != W || lgW >= pa.cb || !pa.sortable()) return false;
+    const uint64_t NBloc = (uint64_t)g.NB / W;
+    if (NBloc < 32) return false;
+    const MsmCfg gl{g.c, g.W, (int)NBloc, g.top_sh};
+    const GroupPlan gp{folded_rows(n, B, g, tv), B};
+    // digits of this rank's points and pass A, destination-major
+    const uint32_t *keys = pass_a_count(wk, wk.grp, pa, gp, g, sc, B, true, W, s);
+    // the key of this batch's slot capacity (the same key, and so the same
+    // capacity, on every rank: the ranks run the same batches in the same order)
+    if (wk.slot_cap.size() > 1024) wk.slot_cap.clear();  // (operator-API batches never repeat a key)
+    const BucketBatch bb{B, tv.table, g, gl, gp, pa, keys, std::make_tuple(wk.batch_seq++, B, tv.n_table)};
+    static const bool slots_on = [] {
+        const char *e = getenv("PNP_MSM_SLOTS");
+        return !(e && atoi(e) == 0);
+    }();
+    std::vector<uint64_t> ts((size_t)B * 48);  // the local results: B weighted sums T, then B plain sums S
+    bool done = false;
+    const auto cap_it = wk.slot_cap.find(bb.key);
+    if (slots_on && W <= SLOT_W_MAX && cap_it != wk.slot_cap.end()) {
+        // (PNP_TEST_SLOT_CAP: a smaller capacity, to exercise the overflow path)
+        static const uint64_t test_cap = [] {
+            const char *e = getenv("PNP_TEST_SLOT_CAP");
+            return e ? strtoull(e, nullptr, 0) : 0ULL;
+        }();
+        const uint64_t cap = test_cap ? std::min(test_cap, cap_it->second) : cap_it->second;
+        done = bucket_slots(wk, bb, cap, ts, s);
+    }
+    if (!done && !bucket_variable(wk, bb, ts, s)) return false;
+    const uint64_t lo_w = (uint64_t)wk.rank * NBloc;  // weight offset of this rank's buckets: its share is T + lo S
     for (int b = 0; b < B; b++) {
         const Xyzz T = get_xyzz(&ts[24 * (size_t)b]), S = get_xyzz(&ts[24 * ((size_t)B + b)]);
         put_xyzz(lo_w ? add(T, mul_small(S, lo_w)) : T, part + 24 * (size_t)b);
@@ -1899,16 +1877,13 @@ uint64_t msm_work_bytes(uint64_t n_pts, uint64_t n_cfg, int fold_c, int B, uint6
     // ranges: the received records sorted into `sorted`
     const uint64_t acc_ent = buckets ? v_bytes / 8 : nent;
     const uint64_t sort = buckets ? acc_ent * 4 : nent * (4 + 2 + 4);
-    const uint64_t S = std::max<uint32_t>(16, acc_segment(acc_ent, true));
-    const uint64_t nthr = (acc_ent + S - 1) / S;
-    const uint64_t acc = (WB + 2 * nthr) * 224 + nthr * 12 + (WB + 1) * 4 + (WB * 24 + WB * 72 + 64) * 8;
-    return digits + counts + sort + acc;
+    return digits + counts + sort + acc_layout(WB, acc_ent, true).total_bytes();
 }
 uint64_t msm_work_held(const MsmWork &wk) {
     const MsmGroup &g = wk.grp;
-    return wk.digits.bytes + wk.part_counts.bytes + wk.rec_counts.bytes + g.counts.bytes + g.offsets.bytes +
-           g.scan_tmp.bytes + g.ent.bytes + g.fkey.bytes + g.sorted.bytes + g.buckets.bytes + g.seg.bytes +
-           g.redo.bytes + g.exc.bytes + g.heavy.bytes + g.wctr.bytes;
+    return wk.digits.bytes + g.counts.bytes + g.offsets.bytes + g.scan_tmp.bytes + g.ent.bytes + g.fkey.bytes +
+           g.sorted.bytes + g.buckets.bytes + g.seg.bytes + g.redo.bytes + g.exc.bytes + g.heavy.bytes +
+           g.wctr.bytes;
 }
 
 void msm_point_range(uint64_t n, int rank, int world, uint64_t &p0, uint64_t &p1) {
@@ -1928,33 +1903,27 @@ void msm_run_batch(MsmWork &wk, const uint64_t *d_points, const uint64_t *const 
         throw Error(PNP_E_ARG);
     }
     if (wk.timer) wk.timer->credit("msm_scalar_bytes", 32.0 * (double)B * n / wk.world);  // (this rank's scalars)
-    if (wk.world == 1) {
-        if (segs)
-            msm_local_batch(wk, nullptr, d_scalars, B, n, h_xyzz, s, table, segs->n_table, 0, segs->off, segs->c);
-        else
-            msm_local_batch(wk, d_points, d_scalars, B, n, h_xyzz, s, table);
-        return;
-    }
-    uint64_t p0, p1;
-    msm_point_range(n, wk.rank, wk.world, p0, p1);
-    std::vector<const uint64_t *> sc(B);
-    for (int b = 0; b < B; b++) sc[b] = scalars_local ? d_scalars[b] : d_scalars[b] + 4 * p0;
-    std::vector<uint64_t> part((size_t)B * 24);
-    // bucket ranges (the folded table covers all n points) or point ranges; a
-    // segmented table covers every point of its sets, or (sliced) this rank's
-    // range of each
-    const bool full = table && (wk.full_table() || (segs && !segs->sliced));
-    const uint64_t n_tab = segs ? segs->n_table : n;
-    const uint64_t *off = segs ? segs->off : nullptr;
+    uint64_t p0 = 0, p1 = n;  // this rank's points
+    if (wk.world > 1) msm_point_range(n, wk.rank, wk.world, p0, p1);
     if (segs && segs->sliced && wk.full_table()) {
         set_error("msm: a sliced segment table in bucket-range mode");
         throw Error(PNP_E_ARG);
     }
-    const int cc = segs ? segs->c : 0;
-    if (!(table && wk.full_table() &&
-          msm_bucket_batch(wk, sc.data(), B, n_tab, p0, p1, part.data(), s, table, off, cc)))
-        msm_local_batch(wk, d_points ? d_points + 12 * p0 : nullptr, sc.data(), B, p1 - p0, part.data(), s, table,
-                        segs ? n_tab : full ? n_tab : 0, full ? p0 : 0, off, cc);
+    // the table covers all n points of every set (bucket ranges, an unsliced
+    // segment table) or this rank's range of each (sliced, or built per rank)
+    const bool full = table && (wk.full_table() || (segs && !segs->sliced));
+    const TableView tv{table, segs ? segs->n_table : full ? n : p1 - p0, full ? p0 : 0, segs ? segs->off : nullptr,
+                       segs ? segs->c : 0};
+    if (wk.world == 1) {
+        msm_local_batch(wk, d_points, d_scalars, B, n, h_xyzz, s, tv);
+        return;
+    }
+    std::vector<const uint64_t *> sc(B);
+    for (int b = 0; b < B; b++) sc[b] = scalars_local ? d_scalars[b] : d_scalars[b] + 4 * p0;
+    std::vector<uint64_t> part((size_t)B * 24);
+    // bucket ranges (the folded table covers all n points) or point ranges
+    if (!(table && wk.full_table() && msm_bucket_batch(wk, sc.data(), B, p1 - p0, part.data(), s, tv)))
+        msm_local_batch(wk, d_points ? d_points + 12 * p0 : nullptr, sc.data(), B, p1 - p0, part.data(), s, tv);
     const std::vector<uint64_t> all = rank_allgather(wk, s, part.data(), B * 24, PNP_EX_TAG_MSM_SUMS);
     for (int b = 0; b < B; b++) {
         Xyzz acc = Xyzz::inf();

@@ -1,6 +1,7 @@
 // msm_internal.h — pieces shared by msm.hip (sort + accumulate) and
 // msm_reduce.hip (bucket reduction, compiled with out-of-line Fq products).
 #pragma once
+#include <algorithm>
 #include "pnp_internal.h"
 
 namespace pnp {
@@ -41,6 +42,35 @@ inline MsmCfg msm_cfg(uint64_t n, int c = 0, bool folded = false) {
     g.top_sh = folded && top_bits >= 0 && g.c - 1 - top_bits > 0 ? g.c - 1 - top_bits : 0;
     return g;
 }
+
+// The scratch of a group's accumulation (msm.hip acc_layout: from WB, the entry
+// bound and `folded`).  Folded, in raw radix-2^29 pieces of P29 u32 (ec29.cuh):
+// seg = bk29 (WB pieces) | head (nthr) | tail (nthr) | tailb (nthr u32) | tlist
+// (1 + nthr u32: count, then the lanes with a tail); redo = count (4 u32) | lanes
+constexpr int WCTR_SLOTS = 64;  // piece counters behind the entry count (msm.hip k_count_pieces)
+struct AccLayout {
+    static constexpr uint64_t P29 = 56;
+    uint64_t WB, nthr;   // buckets; accumulation lanes
+    uint32_t S, pieces;  // entries per lane; typical lanes per bucket
+    uint64_t seg_bytes() const { return ((WB + 2 * nthr) * P29 + 2 * nthr + 1) * 4; }
+    uint64_t redo_bytes() const { return (4 + nthr) * 4; }
+    uint64_t heavy_bytes() const { return (WB + 1) * 4; }
+    uint64_t exc_bytes() const { return 16; }
+    uint64_t wctr_bytes() const { return 8 * (1 + WCTR_SLOTS); }
+    // two users: the 32-bit tree (msm_reduce, also a folded group's exact
+    // fallback: WB R384 buckets | 72 WB u64 of scratch, + 64) and msm_reduce29's
+    // scratch (126 WB + 96 nwin u32, nwin <= WB / 4).  The first is the larger
+    uint64_t buckets_bytes() const { return std::max<uint64_t>((WB * 96 + 64) * 8, (126 * WB + 96 * (WB / 4)) * 4); }
+    uint64_t total_bytes() const {
+        return seg_bytes() + redo_bytes() + heavy_bytes() + exc_bytes() + wctr_bytes() + buckets_bytes();
+    }
+    uint32_t *head(const DevBuf &seg) const { return seg.u32() + P29 * WB; }
+    uint32_t *tail(const DevBuf &seg) const { return head(seg) + P29 * nthr; }
+    uint32_t *tailb(const DevBuf &seg) const { return tail(seg) + P29 * nthr; }
+    uint32_t *tlist(const DevBuf &seg) const { return tailb(seg) + nthr; }
+    uint32_t *redo_lanes(const DevBuf &redo) const { return redo.u32() + 4; }
+    uint64_t *tree(const DevBuf &buckets) const { return buckets.u64() + WB * 24; }  // behind the R384 buckets
+};
 
 // Buckets split across accumulate lanes (S entries per lane): bucket u whose
 // sorted run [offs[u*nch], offs[(u+1)*nch]) spans lanes t0 < t1 is

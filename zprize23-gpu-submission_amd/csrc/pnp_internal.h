@@ -44,8 +44,10 @@ struct DevBuf {
     }
     ~DevBuf() { release(); }
     void alloc(size_t b);
+    void reserve(size_t b) { if (bytes < b) alloc(b); }  // grow-only: the contents are lost when it grows
     void release();
     uint64_t *u64() const { return static_cast<uint64_t *>(p); }
+    uint32_t *u32() const { return static_cast<uint32_t *>(p); }
 };
 
 // ---- NTT (ntt.hip) ----
@@ -138,8 +140,8 @@ struct MsmGroup {
     DevBuf counts, offsets, scan_tmp, ent, fkey, sorted, buckets, seg, redo;
     DevBuf exc;  // folded: an F29 merge / tree addition met equal or opposite operands
     DevBuf heavy;  // folded: the merge's queue of buckets with many pieces
-    uint32_t S = 0, pieces = 0;  // folded: accumulate segment length, pieces per bucket
-    uint64_t nthr = 0;           // folded: accumulate lanes (head / tail slots)
+    uint64_t acc_nent = 0;  // entries the last accumulation was laid out for (msm_internal.h AccLayout)
+    uint32_t exc_h = 0, nredo_h = 0;  // host copies of exc and the redo count, read back with the results
     // timed runs only (KernelTimer enabled): what the last k_accumulate29 launch
     // really did, counted on the device from the bucket starts — {sorted
     // entries, pieces started fresh}; mixed additions = entries - pieces
@@ -179,7 +181,6 @@ struct MsmWork {
     bool ordered = false;
     // the folded table covers ALL n points (bucket ranges gather any point)
     bool full_table() const { return world > 1 && alltoallv != nullptr; }
-    DevBuf part_counts, rec_counts;  // bucket-range pass counts
     // Fixed-slot bucket exchange (msm.hip msm_bucket_batch): every rank sends
     // every peer one slot of `cap` records with the bin counts in the slot's
     // header, so the records move in one equal-size all-to-all with no host

@@ -94,8 +94,7 @@ static uint64_t rec_scratch_elems(uint64_t n) {
 }
 void k_prefix_product(uint64_t *d, uint64_t n, DevBuf &scratch, hipStream_t s) {
     if (!n) return;
-    size_t need = rec_scratch_elems(n) * 32;
-    if (scratch.bytes < need) scratch.alloc(need);
+    scratch.reserve(rec_scratch_elems(n) * 32);
     prefix_product_rec(d, n, scratch.u64(), s);
 }
 
@@ -153,8 +152,7 @@ void k_batch_inverse(uint64_t *d, uint64_t n, DevBuf &scratch, hipStream_t s) {
     if (!n) return;
     uint64_t need = 0, m = n;
     while (m > 4096) { uint64_t nc = (m + CHUNK - 1) / CHUNK; need += m + nc; m = nc; }
-    need = (need + 1) * 32;
-    if (scratch.bytes < need) scratch.alloc(need);
+    scratch.reserve((need + 1) * 32);
     binv_rec(d, n, scratch.u64(), s);
 }
 
@@ -239,8 +237,7 @@ void k_poly_div_linear_batch(uint64_t *const *d, const Fr *z, int K, uint64_t n,
     if (!n) return;
     for (int k0 = 0; k0 < K; k0 += HB_MAX) {
         const int kb = std::min(K - k0, HB_MAX);
-        size_t need = rec_scratch_elems(n) * 32 * kb;
-        if (scratch.bytes < need) scratch.alloc(need);
+        scratch.reserve(rec_scratch_elems(n) * 32 * kb);
         HornerSet hs = {};
         for (int k = 0; k < kb; k++) {
             hs.v[k] = d[k0 + k];
@@ -353,8 +350,7 @@ void k_poly_eval_sets(const EvalSet *sets, int nsets, uint64_t n, DevBuf &scratc
     // has its own slice, so all launch back to back and ONE copy and ONE
     // synchronisation return every value (round 5 evaluates 18 polys at two
     // points: four host round trips before)
-    size_t need = (size_t)total * nb * 32 + (size_t)total * 32 + 64;
-    if (scratch.bytes < need) scratch.alloc(need);
+    scratch.reserve((size_t)total * nb * 32 + (size_t)total * 32 + 64);
     uint64_t *partial = scratch.u64();
     uint64_t *res = partial + (size_t)total * nb * 4;
     int q = 0;  // polys launched so far

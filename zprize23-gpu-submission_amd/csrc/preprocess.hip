@@ -306,8 +306,7 @@ uint64_t wire_sigma(NttTables &ntt, const uint32_t *const d_var[4], uint64_t n_g
     const uint32_t ntiles = (uint32_t)((m + PNP_SIGMA_TILE - 1) / PNP_SIGMA_TILE);
     const uint64_t hist_n = (uint64_t)SORT_BINS * ntiles;
     const uint32_t nseg = (uint32_t)((hist_n + SCAN_SPAN - 1) / SCAN_SPAN);
-    const uint64_t need = wire_sigma_scratch_bytes(n_gates);
-    if (scratch.bytes < need) scratch.alloc(need);
+    scratch.reserve(wire_sigma_scratch_bytes(n_gates));
     uint32_t *buf = static_cast<uint32_t *>(scratch.p);
     uint32_t *key[2] = {buf, buf + m}, *val[2] = {buf + 2 * m, buf + 3 * m};
     uint32_t *hist = buf + 4 * m, *sums = hist + hist_n, *bad = sums + nseg;

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void k_any_nonzero_(const uint64_t *v, uint64_
 // word; one launch, one host synchronisation
 void k_any_nonzero_n(const uint64_t *v, uint64_t words, uint64_t stride, int cnt, bool *nz, DevBuf &scratch,
                      hipStream_t s) {
-    if (scratch.bytes < 4 * (size_t)cnt + 16) scratch.alloc(4 * (size_t)cnt + 16);
+    scratch.reserve(4 * (size_t)cnt + 16);
     unsigned *flag = static_cast<unsigned *>(scratch.p);
     PNP_HIP(hipMemsetAsync(flag, 0, 4 * (size_t)cnt, s));
     if (words) {
@@ -188,7 +188,7 @@ __global__ void k_any_diff_(const uint64_t *a, const uint64_t *b, uint64_t words
 }
 bool k_any_diff(const uint64_t *a, const uint64_t *b, uint64_t words, DevBuf &scratch, hipStream_t s) {
     if (!words) return false;
-    if (scratch.bytes < 16) scratch.alloc(16);
+    scratch.reserve(16);
     unsigned *flag = static_cast<unsigned *>(scratch.p);
     PNP_HIP(hipMemsetAsync(flag, 0, 4, s));
     uint64_t blocks = (words + 255) / 256;
@@ -226,7 +226,7 @@ __global__ void k_hash_words_(const uint64_t *a, uint64_t words, unsigned long l
     }
 }
 void k_hash_words(const uint64_t *a, uint64_t words, DevBuf &scratch, hipStream_t s, uint64_t out[2]) {
-    if (scratch.bytes < 16) scratch.alloc(16);
+    scratch.reserve(16);
     unsigned long long *d = static_cast<unsigned long long *>(scratch.p);
     PNP_HIP(hipMemsetAsync(d, 0, 16, s));
     if (words) {
@@ -261,7 +261,7 @@ __global__ void k_pack_affine_(const uint8_t *src, uint64_t n, uint64_t stride, 
 }
 bool k_pack_affine(const uint8_t *src, uint64_t n, uint64_t stride, uint64_t x_off, uint64_t y_off,
                    uint64_t inf_off, uint64_t *dst, DevBuf &scratch, hipStream_t s) {
-    if (scratch.bytes < 16) scratch.alloc(16);
+    scratch.reserve(16);
     unsigned *bad = static_cast<unsigned *>(scratch.p);
     PNP_HIP(hipMemsetAsync(bad, 0, 4, s));
     hipLaunchKernelGGL(k_pack_affine_, dim3(nblk(n)), dim3(256), 0, s, src, n, stride, x_off, y_off, inf_off, dst,

@@ -517,7 +517,7 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         // 1 / (x_i - w^pos) on this rank's blocks, kept across proofs with the
         // same PI position
         ctx->key.pinv_pos = ~0ULL;
-        if (ctx->key.pinv.bytes < 32 * NB) ctx->key.pinv.alloc(32 * NB);
+        ctx->key.pinv.reserve(32 * NB);
         Fr wpos = pow_u64(root_of_unity(lg), pi_pos[0]);
         k_affine(ctx->key.pinv.u64(), ctx->key.blk[kLin].u64(), Fr::one(), neg(wpos), NB, s);
         k_batch_inverse(ctx->key.pinv.u64(), NB, ctx->scratch_a, s);

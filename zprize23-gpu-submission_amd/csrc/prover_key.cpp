@@ -106,7 +106,7 @@ void pk_sigma_domain(pnp_ctx *ctx, const ProverKeyC &dev, uint64_t D, uint32_t l
     const uint64_t *const *f = reinterpret_cast<const uint64_t *const *>(&dev);
     for (int j = 0; j < 4; j++) {
         DevBuf &sn = ctx->key.sigma_n[j];
-        if (sn.bytes < 32 * D) sn.alloc(32 * D);
+        sn.reserve(32 * D);
         PNP_HIP(hipMemcpyAsync(sn.p, f[kKeyTable[kSig0 + j].coeffs], 32 * D, hipMemcpyDeviceToDevice, ctx->stream));
         ntt_run(ctx->ntt, sn.u64(), lg, false, false, ctx->stream);
     }

@@ -282,7 +282,7 @@ bool z_groups_enabled() {
 
 // hipcub temporary storage, grown on demand
 void *cub_tmp(DevBuf &b, size_t bytes) {
-    if (b.bytes < bytes) b.alloc(bytes);
+    b.reserve(bytes);
     return b.p;
 }
 
