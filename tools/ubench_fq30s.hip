@@ -8,6 +8,15 @@
 // The signed product is checked first: the host's copy of the function
 // against integer arithmetic mod q, then 256 lanes' chains on the GPU against
 // the host's (check() below).
+//
+// CHAIN variants (mul<C>, sqr<C>, mul2<C>): the compiler starts every column's
+// operand products from zero, keeps the carry of the reduction on a second
+// register pair and joins the two with one 64-bit add per column that the
+// source does not contain.  C = 1: an empty asm on the accumulator between two
+// columns (pin()) makes the carry opaque; C = 2: the same, and every partial
+// sum is named in an assumption (mad()).  k_mul30s<C> times the plain product,
+// k_mix30s<C> the mix of one mixed addition (6 products, 2 squares, one
+// a b + c d with one reduction).
 //   hipcc -O3 --offload-arch=gfx950 -I<csrc> ubench_fq30s.hip -o ubench_fq30s
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -30,8 +39,41 @@ struct F30 {
 };
 // low 30 bits of x as a balanced limb in [-2^29, 2^29)
 __host__ __device__ __forceinline__ int32_t bal30(uint32_t x) { return (int32_t)(x << 2) >> 2; }
-__host__ __device__ __forceinline__ int64_t mad(int32_t a, int32_t b, int64_t acc) { return acc + (int64_t)a * b; }
+// CHAIN 2: every partial sum is also named in an assumption (true: a column
+// stays below 2^63), which gives it a second use, so the sums of a column are
+// not merged into one expression and reordered while the assumptions live
+template <int CHAIN = 0>
+__host__ __device__ __forceinline__ int64_t mad(int32_t a, int32_t b, int64_t acc) {
+    acc += (int64_t)a * b;
+#ifdef __HIP_DEVICE_COMPILE__
+    if (CHAIN == 2) __builtin_assume(acc != INT64_MIN);
+#endif
+    return acc;
+}
+__host__ __device__ __forceinline__ int64_t carry(int64_t acc) { return (acc + (1 << 29)) >> 30; }
+// CHAIN: the value is opaque to the compiler from here on, so the additions
+// before and after it cannot be reassociated (device only; emits nothing)
+template <int CHAIN>
+__host__ __device__ __forceinline__ int64_t pin(int64_t acc) {
+#ifdef __HIP_DEVICE_COMPILE__
+    if (CHAIN) asm volatile("" : "+v"(acc));
+#endif
+    return acc;
+}
+// one column of the reduction: returns the carry into column k + 1
+template <int CHAIN>
+__host__ __device__ __forceinline__ int64_t reduce_col(int k, int64_t acc, int32_t *m, int32_t *r) {
+#pragma unroll
+    for (int i = (k > 12 ? k - 12 : 0); i < (k < 13 ? k : 13); i++) acc = mad<CHAIN>(m[i], qlimb(k - i), acc);
+    if (k < 13) {
+        m[k] = bal30((uint32_t)acc * QINV);
+        return mad<CHAIN>(m[k], qlimb(0), acc) >> 30;  // low 30 bits become 0
+    }
+    r[k - 13] = bal30((uint32_t)acc);
+    return carry(acc);
+}
 // a b 2^-390 (mod q), |a|, |b| < 2^385 -> |r| < 2^381; r.l[0..11] balanced
+template <int CHAIN = 0>
 __host__ __device__ __forceinline__ F30 mul(const F30 &a, const F30 &b) {
     int32_t m[13];
     F30 r;
@@ -39,16 +81,49 @@ __host__ __device__ __forceinline__ F30 mul(const F30 &a, const F30 &b) {
 #pragma unroll
     for (int k = 0; k < 25; k++) {
 #pragma unroll
-        for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) acc = mad(a.l[i], b.l[k - i], acc);
+        for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) acc = mad<CHAIN>(a.l[i], b.l[k - i], acc);
+        acc = pin<CHAIN>(reduce_col<CHAIN>(k, acc, m, r.l));
+    }
+    r.l[12] = (int32_t)acc;
+    return r;
+}
+// a^2 2^-390: the cross products once, against the doubled limb
+template <int CHAIN = 0>
+__host__ __device__ __forceinline__ F30 sqr(const F30 &a) {
+    int32_t m[13], a2[13];
 #pragma unroll
-        for (int i = (k > 12 ? k - 12 : 0); i < (k < 13 ? k : 13); i++) acc = mad(m[i], qlimb(k - i), acc);
-        if (k < 13) {
-            m[k] = bal30((uint32_t)acc * QINV);
-            acc = mad(m[k], qlimb(0), acc);  // low 30 bits become 0
-            acc >>= 30;
+    for (int i = 0; i < 13; i++) a2[i] = a.l[i] * 2;
+    F30 r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 25; k++) {
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); 2 * i < k; i++) acc = mad<CHAIN>(a.l[i], a2[k - i], acc);
+        if ((k & 1) == 0) acc = mad<CHAIN>(a.l[k / 2], a.l[k / 2], acc);
+        acc = pin<CHAIN>(reduce_col<CHAIN>(k, acc, m, r.l));
+    }
+    r.l[12] = (int32_t)acc;
+    return r;
+}
+// (a b + c d) 2^-390 with one reduction; in the columns of more than 31
+// products (k = 10..14) the operand products' carry is taken out early
+template <int CHAIN = 0>
+__host__ __device__ __forceinline__ F30 mul2(const F30 &a, const F30 &b, const F30 &c, const F30 &d) {
+    int32_t m[13];
+    F30 r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 25; k++) {
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) {
+            acc = mad<CHAIN>(a.l[i], b.l[k - i], acc);
+            acc = mad<CHAIN>(c.l[i], d.l[k - i], acc);
+        }
+        if (3 * (k < 13 ? k + 1 : 25 - k) > 31) {
+            const int64_t hi = carry(acc);
+            acc = pin<CHAIN>(reduce_col<CHAIN>(k, pin<CHAIN>((int64_t)bal30((uint32_t)acc)), m, r.l) + hi);
         } else {
-            r.l[k - 13] = bal30((uint32_t)acc);
-            acc = (acc + (1 << 29)) >> 30;
+            acc = pin<CHAIN>(reduce_col<CHAIN>(k, acc, m, r.l));
         }
     }
     r.l[12] = (int32_t)acc;
@@ -88,18 +163,46 @@ __host__ __device__ inline void seed30s(uint32_t t, uint32_t seed, f30s::F30 &a,
     }
     a.l[12] >>= 8; b.l[12] >>= 8; c.l[12] >>= 8; d.l[12] >>= 8;
 }
+template <int CHAIN = 0>
 __host__ __device__ inline void chain30s(int L, f30s::F30 &a, f30s::F30 &b, f30s::F30 &c, f30s::F30 &d) {
 #pragma unroll 1
     for (int i = 0; i < L; i++) {
-        a = f30s::mul(a, b); c = f30s::mul(c, d); b = f30s::mul(b, c); d = f30s::mul(d, a);
+        a = f30s::mul<CHAIN>(a, b); c = f30s::mul<CHAIN>(c, d); b = f30s::mul<CHAIN>(b, c); d = f30s::mul<CHAIN>(d, a);
+    }
+}
+// the nine products of one mixed addition: 6 mul, 2 sqr, 1 mul2 (3,055
+// multiply-adds), chained through the four values so that nothing is dead;
+// every output is < 2^382, inside the products' input bound of 2^385
+template <int CHAIN = 0>
+__host__ __device__ inline void mix30s(int L, f30s::F30 &a, f30s::F30 &b, f30s::F30 &c, f30s::F30 &d) {
+#pragma unroll 1
+    for (int i = 0; i < L; i++) {
+        f30s::F30 u = f30s::mul<CHAIN>(a, c), s = f30s::mul<CHAIN>(b, d);
+        f30s::F30 pp = f30s::sqr<CHAIN>(u);
+        f30s::F30 ppp = f30s::mul<CHAIN>(u, pp), q = f30s::mul<CHAIN>(a, pp);
+        a = f30s::sqr<CHAIN>(s);
+        b = f30s::mul2<CHAIN>(s, q, b, ppp);
+        c = f30s::mul<CHAIN>(c, pp);
+        d = f30s::mul<CHAIN>(d, ppp);
     }
 }
 
+template <int CHAIN>
 __global__ __launch_bounds__(256) void k_mul30s(uint32_t *out, int L, uint32_t seed) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     f30s::F30 a, b, c, d;
     seed30s(t, seed, a, b, c, d);
-    chain30s(L, a, b, c, d);
+    chain30s<CHAIN>(L, a, b, c, d);
+    uint32_t x = 0;
+    for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
+    out[t] = x;
+}
+template <int CHAIN>
+__global__ __launch_bounds__(256) void k_mix30s(uint32_t *out, int L, uint32_t seed) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    f30s::F30 a, b, c, d;
+    seed30s(t, seed, a, b, c, d);
+    mix30s<CHAIN>(L, a, b, c, d);
     uint32_t x = 0;
     for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
     out[t] = x;
@@ -144,15 +247,23 @@ static bool divisible_by_q(std::vector<int64_t> v) {  // v: signed limbs radix 2
         if (rem[w]) return false;
     return true;
 }
-static bool check_product(const f30s::F30 &a, const f30s::F30 &b) {
-    const f30s::F30 r = f30s::mul(a, b);
-    std::vector<int64_t> v(27, 0);  // r 2^390 - a b, columns of 13 products < 2^58 and one limb
+// r = (a b + c d) 2^-390 (mod q), c = nullptr: r = a b 2^-390
+static bool check_result(const f30s::F30 &r, const f30s::F30 &a, const f30s::F30 &b, const f30s::F30 *c = nullptr,
+                         const f30s::F30 *d = nullptr) {
+    std::vector<int64_t> v(27, 0);  // r 2^390 - a b - c d, columns of <= 26 products < 2^58 and one limb
     for (int i = 0; i < 13; i++) v[13 + i] += r.l[i];
     for (int i = 0; i < 13; i++)
-        for (int j = 0; j < 13; j++) v[i + j] -= (int64_t)a.l[i] * b.l[j];
+        for (int j = 0; j < 13; j++) {
+            v[i + j] -= (int64_t)a.l[i] * b.l[j];
+            if (c) v[i + j] -= (int64_t)c->l[i] * d->l[j];
+        }
     for (int i = 0; i < 12; i++)
         if (r.l[i] < -(1 << 29) || r.l[i] >= (1 << 29)) return false;
     return divisible_by_q(v);
+}
+static bool check_product(const f30s::F30 &a, const f30s::F30 &b) {
+    return check_result(f30s::mul(a, b), a, b) && check_result(f30s::sqr(a), a, a) &&
+           check_result(f30s::mul2(a, b, b, a), a, b, &b, &a);
 }
 static bool check(uint32_t *dout) {
     f30s::F30 a, b, c, d;
@@ -174,27 +285,37 @@ static bool check(uint32_t *dout) {
         a.l[12] >>= 5; b.l[12] >>= 5;  // |value| < 2^385
         bad += !check_product(a, b);
     }
-    printf("signed product against integer arithmetic mod q on the host: %s\n", bad ? "MISMATCH" : "ok");
-    if (dout) {  // the GPU's chain of lanes 0..255 against the host's
-        hipLaunchKernelGGL(k_mul30s, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
-        uint32_t g[256];
-        if (hipMemcpy(g, dout, sizeof g, hipMemcpyDeviceToHost) != hipSuccess) return false;
-        int gb = 0;
-        for (uint32_t t = 0; t < 256; t++) {
-            seed30s(t, 5u, a, b, c, d);
-            chain30s(3, a, b, c, d);
-            uint32_t x = 0;
-            for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
-            gb += x != g[t];
+    printf("signed products (mul, sqr, mul2) against integer arithmetic mod q on the host: %s\n",
+           bad ? "MISMATCH" : "ok");
+    if (dout) {  // the GPU's chains of lanes 0..255, plain and CHAIN, against the host's
+        for (int v = 0; v < 6; v++) {
+            if (v == 0) hipLaunchKernelGGL(k_mul30s<0>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            if (v == 1) hipLaunchKernelGGL(k_mul30s<1>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            if (v == 2) hipLaunchKernelGGL(k_mul30s<2>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            if (v == 3) hipLaunchKernelGGL(k_mix30s<0>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            if (v == 4) hipLaunchKernelGGL(k_mix30s<1>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            if (v == 5) hipLaunchKernelGGL(k_mix30s<2>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            uint32_t g[256];
+            if (hipMemcpy(g, dout, sizeof g, hipMemcpyDeviceToHost) != hipSuccess) return false;
+            int gb = 0;
+            for (uint32_t t = 0; t < 256; t++) {
+                seed30s(t, 5u, a, b, c, d);
+                if (v < 3) chain30s(3, a, b, c, d);
+                else mix30s(3, a, b, c, d);
+                uint32_t x = 0;
+                for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
+                gb += x != g[t];
+            }
+            printf("GPU %s, CHAIN %d, against the host's, 256 lanes: %s\n", v < 3 ? "mul chain" : "mixed-addition mix",
+                   v % 3, gb ? "MISMATCH" : "ok");
+            bad += gb;
         }
-        printf("GPU chain against the host's, 256 lanes: %s\n", gb ? "MISMATCH" : "ok");
-        bad += gb;
     }
     return bad == 0;
 }
 
 template <typename K>
-static double run(K kern, const char *name, uint32_t *dout, uint32_t threads, int L) {
+static double run(K kern, const char *name, uint32_t *dout, uint32_t threads, int L, double per_iter = 4.0) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
@@ -213,8 +334,8 @@ static double run(K kern, const char *name, uint32_t *dout, uint32_t threads, in
     }
     hipFuncAttributes fa;
     hipFuncGetAttributes(&fa, (const void *)kern);
-    const double prods = 4.0 * L * threads;
-    printf("%-8s best %8.3f ms  worst %8.3f ms  %7.2f G products/s  (%d VGPRs)\n", name, best, worst,
+    const double prods = per_iter * L * threads;
+    printf("%-10s best %8.3f ms  worst %8.3f ms  %7.2f G products/s  (%d VGPRs)\n", name, best, worst,
            prods / best / 1e6, fa.numRegs);
     return prods / best / 1e6;
 }
@@ -226,11 +347,20 @@ int main(int argc, char **argv) {
     uint32_t *dout;
     if (hipMalloc(&dout, threads * 4) != hipSuccess) return 2;
     if (!check(dout)) return 1;
-    double a[3], b[3];
+    double a[3], b[3][3], m[3][3];
+    const double mix = 3055.0 / 338.0;  // a mix iteration is 3,055 multiply-adds: counted as 3055 / 338 products
     for (int i = 0; i < 3; i++) {
         a[i] = run(k_mul29, "mul29", dout, threads, L);
-        b[i] = run(k_mul30s, "mul30s", dout, threads, L);
+        b[0][i] = run(k_mul30s<0>, "mul30s", dout, threads, L);
+        b[1][i] = run(k_mul30s<1>, "mul30s/c1", dout, threads, L);
+        b[2][i] = run(k_mul30s<2>, "mul30s/c2", dout, threads, L);
+        m[0][i] = run(k_mix30s<0>, "mix30s", dout, threads, L / 2, mix);
+        m[1][i] = run(k_mix30s<1>, "mix30s/c1", dout, threads, L / 2, mix);
+        m[2][i] = run(k_mix30s<2>, "mix30s/c2", dout, threads, L / 2, mix);
     }
-    for (int i = 0; i < 3; i++) printf("ratio mul30s / mul29 = %.3f\n", b[i] / a[i]);
+    for (int i = 0; i < 3; i++) printf("ratio mul30s / mul29 = %.3f\n", b[0][i] / a[i]);
+    for (int c = 1; c < 3; c++)
+        for (int i = 0; i < 3; i++)
+            printf("ratio CHAIN %d / plain: mul30s %.4f  mix30s %.4f\n", c, b[c][i] / b[0][i], m[c][i] / m[0][i]);
     return 0;
 }

@@ -18,6 +18,20 @@
 // of q); negation is 13 limb negations.  The bounds of the mixed addition are
 // tracked in madd30s (msm.hip) and checked by tests/test_field30s.py against
 // a Python model.
+//
+// One accumulator chain: in the source the carry of column k is the addend of
+// column k + 1's first multiply-add.  Left alone, the compiler reorders a
+// column's sum: it starts the operand products from zero, keeps the carry on a
+// second register pair and joins the two with a 64-bit add the source does not
+// contain (25 a product).  Two things together keep the source's order
+// (tools/ubench_fq30s.hip, profiles/acc_chain_ubench.txt, profiles/
+// acc_chain_isa.txt): the carry handed to the next column goes through an empty
+// asm (pin30s), and every partial sum is named in an assumption (mad30s), which
+// gives it a second use, so the sums of a column are not merged into one
+// expression.  Neither emits an instruction; the compiler pads some of the asm
+// statements with an s_nop 0.  Every column still sums the same terms in the
+// same order as before, so the bounds stated at each product cover every
+// partial sum, and the assumption (a sum is not -2^63) follows from them.
 #pragma once
 #include "field29.cuh"
 #include "f30s_consts.inc"
@@ -30,14 +44,24 @@ struct F30s {
 
 // low 30 bits of x as a balanced limb in [-2^29, 2^29) (v_bfe_i32)
 __device__ __forceinline__ int32_t bal30(uint32_t x) { return (int32_t)(x << 2) >> 2; }
-// acc + a b, one v_mad_i64_i32
-__device__ __forceinline__ int64_t mad30s(int32_t a, int32_t b, int64_t acc) { return acc + (int64_t)a * b; }
+// acc + a b, one v_mad_i64_i32; |acc + a b| < 2^63 by the column bounds below
+__device__ __forceinline__ int64_t mad30s(int32_t a, int32_t b, int64_t acc) {
+    acc += (int64_t)a * b;
+    __builtin_assume(acc != INT64_MIN);
+    return acc;
+}
+// the value as it is, but opaque to the compiler: what is added to it later
+// cannot be reassociated with what was added before
+__device__ __forceinline__ int64_t pin30s(int64_t acc) {
+    asm volatile("" : "+v"(acc));
+    return acc;
+}
 // what a column hands to the next once its balanced low limb is taken out
 __device__ __forceinline__ int64_t carry30(int64_t acc) { return (acc + (1 << 29)) >> 30; }
 
 // one column of the Montgomery reduction: the products m_i q_(k-i) so far,
 // then (k < 13) the new m_k, which clears the low 30 bits, or (k >= 13) the
-// result limb; returns the carry into column k + 1
+// result limb; returns the carry into column k + 1, which the caller pins
 __device__ __forceinline__ int64_t reduce_col30s(int k, int64_t acc, int32_t *m, F30s &r) {
 #pragma unroll
     for (int i = (k > 12 ? k - 12 : 0); i < (k < 13 ? k : 13); i++) acc = mad30s(m[i], F30S_Q[k - i], acc);
@@ -59,7 +83,7 @@ __device__ __forceinline__ F30s mul30s(const F30s &a, const F30s &b) {
     for (int k = 0; k < 25; k++) {
 #pragma unroll
         for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) acc = mad30s(a.l[i], b.l[k - i], acc);
-        acc = reduce_col30s(k, acc, m, r);
+        acc = pin30s(reduce_col30s(k, acc, m, r));
     }
     r.l[12] = (int32_t)acc;
     return r;
@@ -80,7 +104,7 @@ __device__ __forceinline__ F30s sqr30s(const F30s &a) {
 #pragma unroll
         for (int i = (k > 12 ? k - 12 : 0); 2 * i < k; i++) acc = mad30s(a.l[i], a2[k - i], acc);
         if ((k & 1) == 0) acc = mad30s(a.l[k / 2], a.l[k / 2], acc);
-        acc = reduce_col30s(k, acc, m, r);
+        acc = pin30s(reduce_col30s(k, acc, m, r));
     }
     r.l[12] = (int32_t)acc;
     return r;
@@ -91,7 +115,8 @@ __device__ __forceinline__ F30s sqr30s(const F30s &a) {
 // the middle, which does not fit 63 bits.  In the columns of more than 31
 // products (k = 10..14) the carry of the 2 n operand products (<= 26 2^58) is
 // taken out before the reduction products go in, and handed to column k + 1
-// with theirs.  338 + 169 multiply-adds against the 676 of two mul30s.
+// with theirs; the low limb the reduction starts from is pinned like a carry.
+// 338 + 169 multiply-adds against the 676 of two mul30s.
 // |result| < (|a b| + |c d|) 2^-390 + q/2: < 2^382 for inputs < 2^385.
 __device__ __forceinline__ F30s mul2_30s(const F30s &a, const F30s &b, const F30s &c, const F30s &d) {
     int32_t m[13];
@@ -108,7 +133,7 @@ __device__ __forceinline__ F30s mul2_30s(const F30s &a, const F30s &b, const F30
             const int64_t hi = carry30(acc);
             acc = reduce_col30s(k, (int64_t)bal30((uint32_t)acc), m, r) + hi;
         } else {
-            acc = reduce_col30s(k, acc, m, r);
+            acc = pin30s(reduce_col30s(k, acc, m, r));
         }
     }
     r.l[12] = (int32_t)acc;
