@@ -3,7 +3,10 @@ mixed addition of the MSM bucket accumulation): every routine restated in
 Python limb for limb, with the signed 64-bit column accumulator and the 32-bit
 limb sums asserted at every step; the worst-case column sums from limb
 magnitudes alone (not from random inputs); an interval analysis of the mixed
-addition; agreement with plain modular arithmetic; the table and piece forms."""
+addition; agreement with plain modular arithmetic; the table and piece forms.
+This file checks the Python model; the compiled device routines themselves run
+on the same edge lists in tests/test_gpu_dev_arith.py (tests/native/
+dev_arith.hip), limb for limb against this model."""
 import os
 import random
 import re
@@ -346,7 +349,7 @@ def test_piece_form():
 
 # ---------------------------------------------------------------- mixed addition
 def madd30s(p, x2, y2):
-    """madd30s of msm.hip"""
+    """madd30s of ec30s.cuh"""
     X, Y, ZZ, ZZZ = p
     u2, s2 = mul30s(x2, ZZ), mul30s(y2, ZZZ)
     P, R = sub30s(u2, X), sub30s(s2, Y)

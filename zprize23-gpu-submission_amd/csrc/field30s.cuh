@@ -16,7 +16,7 @@
 // (a b + M q) 2^-390 with |M| < 2^389, so |result| < 2^380 + q/2 < 2^381.
 // Subtraction is limb-wise with the carries renormalised (no lifted multiples
 // of q); negation is 13 limb negations.  The bounds of the mixed addition are
-// tracked in madd30s (msm.hip) and checked by tests/test_field30s.py against
+// tracked in madd30s (ec30s.cuh) and checked by tests/test_field30s.py against
 // a Python model.
 //
 // One accumulator chain: in the source the carry of column k is the addend of
