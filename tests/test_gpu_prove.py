@@ -99,6 +99,72 @@ def test_gen_proof_v2_resident(tmp_path):
     ctx.close()
 
 
+_R45 = ["r4_lde", "r4_quotient", "r4_intt8", "r4_commit", "r5_evals"]
+
+
+@pytest.mark.parametrize("satisfying", [True, False])
+def test_stage_order(satisfying):
+    """The exact ordered stage names of a resident-key proof (bench.py and the
+    tools under tools/ read them): rounds 4 and 5 up to the identity check
+    stand once for a satisfying witness and twice (6 blocks, then all 8) for
+    an unsatisfied one; round 6 always stands once."""
+    import pnp
+    inp = Inputs(8, 12, satisfying=satisfying)
+    exp = inp.oracle_proof()
+    ctx = pnp.Context(0)
+    ctx.load_prover_key(inp.pk, inp.n, device_ptrs=False)
+    ctx.load_commit_key(inp.ck, inp.n, device_ptrs=False)
+    ctx.kernel_timing(True)
+    got = ctx.prove(inp.circuit, device_ptrs=False)
+    assert abi.proof_to_bytes(got) == abi.proof_to_bytes(exp)
+    assert ctx.kernel_bytes("quotient_all_blocks") == (0 if satisfying else 1)
+    names = [n for n, _ in ctx.stage_times()]
+    assert names == (["inputs", "r1_intt", "r1_commit", "r2_lookup", "r3_z", "r3_z2_pi"]
+                     + _R45 * (1 if satisfying else 2) + ["r5_lin", "r6_witness", "r6_commit"])
+    ctx.close()
+
+
+@pytest.mark.parametrize("switch,value,satisfying,redo", [
+    ("PNP_NO_OVERLAP", "1", True, None),
+    ("PNP_QUOT29", "0", True, 0),
+    ("PNP_QUOT_BLOCKS", "7", True, 0),
+    ("PNP_QUOT_BLOCKS", "7", False, 1),   # the redo goes from 7 to 8 blocks
+    ("PNP_QUOT_BLOCKS", "8", False, 0),   # all 8 blocks at once: no check, no redo
+])
+def test_prover_switches_same_proof(switch, value, satisfying, redo):
+    """The operator switches that decide branches inside the prover
+     leave the proof byte for byte the oracle's; redo = the
+    expected quotient_all_blocks count.  Each case runs in a fresh child
+    process: the switches are read once per process."""
+    import os
+    import subprocess
+    import sys
+    here = os_path_tests()
+    code = (
+        "import sys; sys.path[:0] = [%r, %r]\n"
+        "from pnp import abi\n"
+        "from pnp_testlib import Inputs\n"
+        "import pnp\n"
+        "inp = Inputs(8, 61, satisfying=%r)\n"
+        "exp = inp.oracle_proof()\n"
+        "ctx = pnp.Context(0)\n"
+        "ctx.load_prover_key(inp.pk, inp.n, device_ptrs=False)\n"
+        "ctx.load_commit_key(inp.ck, inp.n, device_ptrs=False)\n"
+        "ctx.kernel_timing(True)\n"
+        "got = ctx.prove(inp.circuit, device_ptrs=False)\n"
+        "redo = ctx.kernel_bytes('quotient_all_blocks')\n"
+        "ctx.close()\n"
+        "assert abi.proof_to_bytes(got) == abi.proof_to_bytes(exp)\n"
+        "print('SAME redo=%%d' %% redo)\n"
+    ) % (here, os.path.join(os.path.dirname(here), "zprize23-gpu-submission_amd"), satisfying)
+    env = dict(os.environ, **{switch: value})
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "SAME" in r.stdout
+    if redo is not None:
+        assert "redo=%d" % redo in r.stdout
+
+
 def test_synth_circuit_matches_cpu_generator():
     """pnp_synth_circuit (bench generator) == tests' satisfying_witness."""
     import numpy as np

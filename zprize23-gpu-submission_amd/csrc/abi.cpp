@@ -1077,34 +1077,14 @@ uint32_t pnp_proof_infinity_mask(const ProofC *p) {
 
 int pnp_prove(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out) {
     if (!ctx || !cs || !out) return PNP_E_ARG;
-    try {
-        return prove_impl(ctx, cs, device_ptrs, out);
-    } catch (const Error &e) {
-        return e.code;
-    } catch (const std::exception &e) {  // (bad_alloc, system_error: never across the C ABI)
-        set_error("exception: %s", e.what());
-        return PNP_E_DEVICE;
-    } catch (...) {
-        set_error("unknown exception");
-        return PNP_E_DEVICE;
-    }
+    PNP_TRY(prove_impl(ctx, cs, device_ptrs, out));
 }
 
 int pnp_prove_ex(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t n_pi, const uint64_t *pi_pos,
                  const uint64_t *pi_canon, const char *label, ProofC *out) {
     if (!ctx || !cs || !out || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
     ProveOpts o{n_pi, pi_pos, pi_canon, label ? label : "Merkle tree"};
-    try {
-        return prove_impl(ctx, cs, device_ptrs, out, &o);
-    } catch (const Error &e) {
-        return e.code;
-    } catch (const std::exception &e) {
-        set_error("exception: %s", e.what());
-        return PNP_E_DEVICE;
-    } catch (...) {
-        set_error("unknown exception");
-        return PNP_E_DEVICE;
-    }
+    PNP_TRY(prove_impl(ctx, cs, device_ptrs, out, &o));
 }
 
 int pnp_prove_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, int device_ptrs, uint64_t n_pi,
@@ -1116,17 +1096,7 @@ int pnp_prove_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, 
     }
     ProveOpts o{n_pi, pi_pos, pi_canon, label ? label : "Merkle tree"};
     Assignment a{values, n_vars};
-    try {
-        return prove_impl(ctx, nullptr, device_ptrs, out, &o, &a);
-    } catch (const Error &e) {
-        return e.code;
-    } catch (const std::exception &e) {
-        set_error("exception: %s", e.what());
-        return PNP_E_DEVICE;
-    } catch (...) {
-        set_error("unknown exception");
-        return PNP_E_DEVICE;
-    }
+    PNP_TRY(prove_impl(ctx, nullptr, device_ptrs, out, &o, &a));
 }
 
 int pnp_last_stage_times(pnp_ctx *ctx, double *ms, const char **names, int cap) {

@@ -197,12 +197,13 @@ struct Assignment {
 };
 // The witness comes from the columns of `cs`, or, with `asg` (then cs is
 // nullptr and opt is given), from the assignment: the domain is the resident
-// key's, the gates and q_lookup rows the resident wire map's.
-int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt = nullptr,
-               const Assignment *asg = nullptr);
+// key's, the gates and q_lookup rows the resident wire map's.  Throws Error.
+void prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt = nullptr,
+                const Assignment *asg = nullptr);
 }  // namespace pnp
 
-// the body of a v2 entry point: codes, never exceptions, across the C ABI
+// the body of a v2 entry point: codes, never exceptions (bad_alloc,
+// system_error, anything else), across the C ABI
 #define PNP_TRY(...)                                   \
     try {                                              \
         __VA_ARGS__;                                   \
@@ -211,5 +212,8 @@ int prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, c
         return e.code;                                 \
     } catch (const std::exception &e) {                \
         ::pnp::set_error("exception: %s", e.what());   \
+        return PNP_E_DEVICE;                           \
+    } catch (...) {                                    \
+        ::pnp::set_error("unknown exception");         \
         return PNP_E_DEVICE;                           \
     }

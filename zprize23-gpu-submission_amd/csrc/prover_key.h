@@ -169,6 +169,8 @@ struct ResidentKey {
     DevBuf blk[kKeyRows], blk29[kKeyRows];
     int mb0 = 0, nb = 8, blk_rank = 0, blk_world = 1;
     bool std_coset = false, q29 = false;
+    // the array of row r this key's quotient kernel reads (nullptr: absent)
+    const uint64_t *key_block(KeyPoly r) const { return (q29 && kKeyTable[r].in29 ? blk29[r] : blk[r]).u64(); }
     DevBuf pinv;  // 1 / (x - w^pos) (block layout), pos = pinv_pos
     uint64_t pinv_pos = ~0ULL;
 
