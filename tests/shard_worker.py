@@ -76,7 +76,7 @@ def main():
     elif mode == "hbm":
         # one rank short of HBM (PNP_TEST_SHORT_RANK): every rank's first
         # proof must fail with PNP_E_NOMEM naming that rank, before any work
-        # (abi.cpp hbm_budget)
+        # (context.cpp hbm_budget)
         short = int(os.environ["PNP_TEST_SHORT_RANK"])
         if rank == short:
             os.environ["PNP_HBM_LIMIT"] = "1"

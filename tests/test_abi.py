@@ -57,6 +57,21 @@ def test_proof_infinity_mask_host():
     assert [k for k, v in flags.items() if v] == ["f_comm", "h_1_comm", "h_2_comm", "t_7_comm", "t_8_comm"]
 
 
+def test_last_error_is_per_thread_and_readable():
+    """pnp_last_error (abi.cpp) returns the message buffer that set_error
+    (context.cpp) writes, one per thread: readable before any error, and empty
+    on a thread that has made no failing call."""
+    import threading
+    import pnp
+    lib = pnp.load()
+    assert isinstance(lib.pnp_last_error(), bytes)
+    got = []
+    t = threading.Thread(target=lambda: got.append(lib.pnp_last_error()))
+    t.start()
+    t.join()
+    assert got == [b""]
+
+
 def test_ark_g1_affine_layout_shape():
     from pnp import abi
     L = abi.ARK_G1_AFFINE

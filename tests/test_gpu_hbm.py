@@ -1,4 +1,4 @@
-"""HBM budget of a proof (abi.cpp hbm_plan / hbm_budget, pnp_hbm_usage):
+"""HBM budget of a proof (context.cpp hbm_plan / hbm_budget, pnp_hbm_usage):
 
   * the plan pnp_load_prover_key budgets with is an upper bound of what the
     first proof really allocates (the library's own allocation counter), and

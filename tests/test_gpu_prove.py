@@ -349,3 +349,133 @@ def test_v1_strict_envelope(monkeypatch, tmp_path):
 def os_path_tests():
     import os
     return os.path.dirname(os.path.abspath(__file__))
+
+
+# The rows of the v1 call's contract (csrc/v1.cpp, its header comment) that the
+# tests above do not reach.  The call's state is per process, so each case is
+# a script run in a fresh child: n = 2^8 (one domain change to 2^9), the oracle
+# proof as the expected bytes.
+_V1_CHILD = """
+import ctypes as C, os, sys
+sys.path[:0] = [%r, %r]
+import pnp
+from pnp import abi
+from pnp_testlib import Inputs
+lib = pnp.load()
+def same(p, inp):
+    return abi.proof_to_bytes(p) == abi.proof_to_bytes(inp.oracle_proof())
+def v1_stages():
+    ms, names = (C.c_double * 96)(), (C.c_char_p * 96)()
+    k = lib.pnp_last_stage_times(C.c_void_p(lib.pnp_v1_context()), ms, names, 96)
+    assert 0 < k <= 96
+    return [(names[i].decode(), ms[i]) for i in range(k)]
+"""
+
+
+def _v1_child(body, **env):
+    import os
+    import subprocess
+    import sys
+    import textwrap
+    here = os_path_tests()
+    code = _V1_CHILD % (here, os.path.join(os.path.dirname(here), "zprize23-gpu-submission_amd"))
+    return subprocess.run([sys.executable, "-c", code + textwrap.dedent(body)], env=dict(os.environ, **env),
+                          capture_output=True, text=True, timeout=240)
+
+
+_V1_COLD_HEAD = ["v1_ctx_create", "v1_load_prover_key", "v1_load_commit_key", "v1_prove"]
+_V1_COLD_TAIL = ["v1_hash_wait", "v1_call"]
+
+
+def test_v1_cold_stage_list():
+    """A fresh process's first gen_proof (both keys need loading) publishes its
+    own stages around the proof's; the second call on the unchanged keys proves
+    beside the hash and publishes the proof's stages alone."""
+    r = _v1_child("""
+        inp = Inputs(8, 71)
+        assert same(lib.gen_proof(inp.circuit, inp.pk, inp.ck), inp)
+        cold = [n for n, _ in v1_stages()]
+        assert same(lib.gen_proof(inp.circuit, inp.pk, inp.ck), inp)
+        warm = [n for n, _ in v1_stages()]
+        ctx = pnp.Context(0)
+        ctx.load_prover_key(inp.pk, inp.n, device_ptrs=False)
+        ctx.load_commit_key(inp.ck, inp.n, device_ptrs=False)
+        assert same(ctx.prove(inp.circuit, device_ptrs=False), inp)
+        v2 = [n for n, _ in ctx.stage_times()]
+        ctx.close()
+        assert v2 and not any(n.startswith("v1_") for n in v2), v2
+        assert cold == %r + v2 + %r, cold
+        assert warm == v2, warm
+        print("DONE")
+    """ % (_V1_COLD_HEAD, _V1_COLD_TAIL))
+    assert r.returncode == 0 and "DONE" in r.stdout, r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("no_speculate", [False, True])
+def test_v1_strict_on_resident_context(no_speculate):
+    """PNP_V1_STRICT=1 after the first call: the key buffers of a Merkle-class
+    key that proved are rewritten to a key with live q_m / q_lookup selectors;
+    the next call sees the change (by the hash beside the proof on the
+    resident keys, or with PNP_V1_NO_SPECULATE by the hash first), loads the
+    key and refuses it."""
+    env = {"PNP_V1_STRICT": "1"}
+    if no_speculate:
+        env["PNP_V1_NO_SPECULATE"] = "1"
+    r = _v1_child("""
+        inp = Inputs(8, 47)
+        live = Inputs(8, 47, qm_qlookup_evals=True)
+        assert same(lib.gen_proof(inp.circuit, inp.pk, inp.ck), inp)
+        print("FIRST", flush=True)
+        for name, arr in inp.arrays.items():
+            if live.arrays[name].shape == arr.shape:
+                arr[...] = live.arrays[name]
+        for f in ("q_m_coeffs", "q_m_evals", "q_lookup_coeffs", "q_lookup_evals"):
+            if f not in inp.arrays:
+                inp.arrays[f] = live.arrays[f]
+        inp._build_structs()
+        lib.gen_proof(inp.circuit, inp.pk, inp.ck)
+        print("SECOND", flush=True)
+    """, **env)
+    assert "FIRST" in r.stdout, r.stderr[-2000:]
+    assert r.returncode != 0 and "SECOND" not in r.stdout and "PNP_V1_STRICT" in r.stderr, r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("reuse", [False, True])
+def test_v1_reload(reuse):
+    """PNP_V1_RELOAD=1 uploads both keys on every call: a word rewritten
+    between two calls, one the reuse fingerprint does not sample, is read, also
+    with PNP_V1_REUSE=1 set beside it (RELOAD decides the loading)."""
+    env = {"PNP_V1_RELOAD": "1"}
+    if reuse:
+        env["PNP_V1_REUSE"] = "1"
+    r = _v1_child("""
+        inp = Inputs(8, 72)
+        first = lib.gen_proof(inp.circuit, inp.pk, inp.ck)
+        assert same(first, inp)
+        assert same(lib.gen_proof(inp.circuit, inp.pk, inp.ck), inp)
+        qc = inp.arrays["q_c_evals"]
+        assert (qc.size - 1) // 256 > 15   # element 3: between two sampled words
+        qc[3] = qc[5]
+        got = lib.gen_proof(inp.circuit, inp.pk, inp.ck)
+        assert abi.proof_to_bytes(got) != abi.proof_to_bytes(first)
+        assert same(got, inp)
+        print("DONE")
+    """, **env)
+    assert r.returncode == 0 and "DONE" in r.stdout, r.stderr[-2000:]
+
+
+def test_v1_domain_change():
+    """2^8, 2^9, then the 2^8 input again, default mode: the second and third
+    calls find keys resident at another domain and take the cold call's path on
+    the context that exists (v1_ctx_create reported as 0)."""
+    r = _v1_child("""
+        a, b = Inputs(8, 73), Inputs(9, 74)
+        for k, inp in enumerate((a, b, a)):
+            assert same(lib.gen_proof(inp.circuit, inp.pk, inp.ck), inp), k
+            st = v1_stages()
+            names = [n for n, _ in st]
+            assert names[:4] == %r and names[-2:] == %r, (k, names)
+            assert (st[0][1] > 0) == (k == 0), (k, st[0])
+        print("DONE")
+    """ % (_V1_COLD_HEAD, _V1_COLD_TAIL))
+    assert r.returncode == 0 and "DONE" in r.stdout, r.stderr[-2000:]

@@ -20,7 +20,7 @@ struct pnp_ctx {
     pnp::NttTables ntt;
     pnp::MsmWork msm;
     pnp::DevBuf scratch_a, scratch_b;
-    // pinned staging of the host -> HBM uploads (abi.cpp h2d_batch): per copy
+    // pinned staging of the host -> HBM uploads (context.cpp h2d_batch): per copy
     // thread two chunks, a stream and an event per chunk; made on first use
     static constexpr int kStgThreads = 6;
     void *stg_buf[2 * kStgThreads] = {};
@@ -109,7 +109,7 @@ struct pnp_ctx {
 };
 
 namespace pnp {
-// bytes a proof at domain n still has to allocate on this rank (abi.cpp)
+// bytes a proof at domain n still has to allocate on this rank (context.cpp)
 struct HbmPlan {
     uint64_t mandatory = 0;  // per-proof buffers, NTT tables, commit-key table, MSM work
     uint64_t lag = 0;        // the Lagrange-basis key and its folded table (optional)
@@ -139,6 +139,17 @@ struct H2D {
     size_t bytes;
 };
 void h2d_batch(pnp_ctx *ctx, const std::vector<H2D> &copies);
+// device bytes held by every DevBuf of the process, now and at most (pnp_hbm_usage)
+extern std::atomic<uint64_t> g_dev_live, g_dev_peak;
+// shared by context.cpp and abi.cpp only: kept out of the library's exports
+#define PNP_HIDDEN __attribute__((visibility("hidden")))
+// free the staging pool (pnp_ctx_destroy)
+PNP_HIDDEN void h2d_release(pnp_ctx *ctx);
+// this thread's last error message (set_error writes it, pnp_last_error returns it)
+PNP_HIDDEN const char *last_error();
+// the end of every commitment: B XYZZ sums (24 words each) to affine on the
+// host, x and y into out[b]
+PNP_HIDDEN void store_affine(const uint64_t *xyzz, int B, CommitmentC *const *out);
 // the folded table of the Lagrange-basis SRS of size n (this rank's point
 // range), nullptr when it is unavailable (PNP_LAGRANGE=0, n not a power of
 // two or above the key, degenerate key)
@@ -161,7 +172,7 @@ void wire_bases_reset(pnp_ctx *ctx);
 // build the copy-constraint groups now if they are enabled and missing
 // (wires.hip; the background table build)
 void wire_bases_build(pnp_ctx *ctx, uint64_t n);
-// ---- the background table build (abi.cpp; see pnp_ctx::bg) ----
+// ---- the background table build (context.cpp; see pnp_ctx::bg) ----
 // start it after a deferring proof (world 1)
 void tables_start_background(pnp_ctx *ctx, uint64_t n);
 // PNP_DEFER_BG (default on): world-1 deferral builds in the background

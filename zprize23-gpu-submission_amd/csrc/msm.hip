@@ -1778,7 +1778,7 @@ static bool msm_bucket_batch(MsmWork &wk, const uint64_t *const *sc, int B, uint
 int msm_fold_c(uint64_t n_points, int fold_c) { return msm_cfg(n_points, fold_c, true).c; }
 
 // ---- HBM of the MSM machinery (upper bounds for the key-load budget,
-// abi.cpp hbm_plan; checked against the measured peak by tests/test_gpu_hbm.py)
+// context.cpp hbm_plan; checked against the measured peak by tests/test_gpu_hbm.py)
 uint64_t msm_table_bytes(uint64_t n_points, uint64_t n_cfg, int fold_c) {
     return (uint64_t)msm_cfg(n_cfg, fold_c, true).W * n_points * PT29 * 4;
 }

@@ -122,7 +122,7 @@ struct KernelTimer {
     }
 };
 
-// Background table builds (abi.cpp tables_start_background): on the builder's
+// Background table builds (context.cpp tables_start_background): on the builder's
 // thread every build kernel is followed by bg_step, which waits for it (one
 // build kernel in flight at a time, so a proof's streams never queue behind
 // more than one of them on a shared hardware queue) and stops the build when

@@ -392,7 +392,7 @@ void Proof::load_witness() {
     qlk_rows = ng;
     if (asg) {
         const uint64_t *vals = asg->values;
-        if (!device_ptrs) {  // one staged upload (abi.cpp h2d_batch)
+        if (!device_ptrs) {  // one staged upload (context.cpp h2d_batch)
             uint64_t *dv = ctx->buf("asg_values", asg->n_vars);
             h2d_batch(ctx, {{dv, vals, 32 * asg->n_vars}});
             inputs_h2d = 32.0 * asg->n_vars;
@@ -409,7 +409,7 @@ void Proof::load_witness() {
         alg(4.0 * (ng / 8.0 + ng + n));  // ids, gathered values, padded columns
     } else {
         const uint64_t *wsrc[4] = {cs->w_l, cs->w_r, cs->w_o, cs->w_4};
-        std::vector<H2D> up;  // a host witness: staged uploads (abi.cpp h2d_batch)
+        std::vector<H2D> up;  // a host witness: staged uploads (context.cpp h2d_batch)
         for (int j = 0; j < 4; j++) {
             if (device_ptrs) PNP_HIP(hipMemcpyAsync(wsc[j], wsrc[j], 32 * ng, hipMemcpyDeviceToDevice, s));
             else up.push_back({wsc[j], wsrc[j], 32 * ng});

@@ -1,6 +1,6 @@
 // prover_key.h — the one description of the prover key's polynomials, and the
 // key as it is resident in HBM (prover_key.cpp: the loads; prover.cpp: the
-// quotient's arguments; abi.cpp: the v1 hashing).
+// quotient's arguments; v1.cpp: the v1 hashing).
 #pragma once
 #include "pnp_internal.h"
 #include <stddef.h>

@@ -208,7 +208,7 @@ class SoloExchange(WindowExchange):
     #    this rank what this rank sends rank s (alltoallv below returns those
     #    segments), so this rank accumulates as many distinct entries as a real
     #    rank, spread over its bucket range like a real rank's.
-    #  * the key load's device ids (abi.cpp hbm_budget): the other ranks of a
+    #  * the key load's device ids (context.cpp hbm_budget): the other ranks of a
     #    real run have GPUs of their own, so their slots get other ids (the
     #    rank's HBM budget is its whole GPU, as in the real run).
     TAG_T_FLAGS = 0x7F1A6500
