@@ -423,8 +423,9 @@ int pnp_prove_ex(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t n_p
  * row n_gates on, are written by one gather launch into the prover's padded
  * witness buffers; from round 1 on the prover is pnp_prove_ex's, and the proof
  * is byte for byte the one pnp_prove_ex returns for those columns and the
- * key's q_lookup rows.  The assignment is not checked to satisfy the circuit
- * (an unsatisfied one proves like unsatisfied columns do).  Single GPU.
+ * key's q_lookup rows.  Whether the assignment satisfies the circuit is what
+ * pnp_check_assignment (below) tells, row by row; this call does not look (an
+ * unsatisfied one proves like unsatisfied columns do).  Single GPU.
  * Afterwards pnp_last_stage_times carries one extra entry, a count:
  * inputs_h2d_bytes = 32 n_vars for host values, 0 for HBM values; the gather
  * is timed as "gather_witness" (pnp_kernel_timing).
@@ -433,6 +434,72 @@ int pnp_prove_ex(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t n_p
 int pnp_prove_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, int device_ptrs,
                          uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
                          const char *label, ProofC *out);
+
+/* Does a witness satisfy the resident key's circuit?  The row-by-row check of
+ * the ZK-Garage composer's check_circuit_satisfied, on the GPU: every
+ * constraint is evaluated alone on every row of the domain, not folded with a
+ * separation challenge, so a failure names its row and its constraint.  (The
+ * prover itself only notices that round 5's identity fails, redoes rounds 4-6
+ * on all 8 coset blocks and returns PNP_OK with a proof no verifier accepts.)
+ * pnp_check_assignment takes the arguments of pnp_prove_assignment, and
+ * pnp_check_witness those of pnp_prove_ex, each without the label and the
+ * proof; public inputs exactly as pnp_prove_ex.  Only the prover key is needed
+ * (no commit key).  Wires at rows >= n_gates are zero, "next" is row
+ * (i + 1) mod D, all D rows are checked.
+ *   A custom-gate constraint k of a family is violated at row i when the
+ * family's selector row is non-zero and constraint k alone is non-zero
+ * (k in the order of the reference's widgets):
+ *   ARITH      0: q_arith (q_m ab + q_l a + q_r b + q_o c + q_4 d + q_hl a^5 +
+ *                 q_hr b^5 + q_h4 d^5 + q_c) + PI_i != 0
+ *   RANGE      0..3: delta(c - 4d), delta(b - 4c), delta(a - 4b), delta(d_next - 4a)
+ *   LOGIC      0..4: delta(a'), delta(b'), delta(d'), c - a'b', delta_xor_and,
+ *                 with a' = a_next - 4a and so on
+ *   FIXED_ADD  0..3: bit consistency, bit q_c - c, the x equation, the y equation
+ *   VAR_ADD    0..2: x1 y2 - d_next, the x3 equation, the y3 equation
+ *   LOOKUP     with k the key's q_lookup row value, s the caller's (cs->q_lookup,
+ *              zero from cs->n on; the assignment form has s = k) and T the
+ *              resident table of D rows —  0: s != 0 and (a, b, c, d) is no row
+ *              of T, compared exactly on all 4 x 256 bits;  1: s = 0, k != 0 and
+ *              (a, b, c, d) differs from T's row 0 (the prover queries T[0]
+ *              where s = 0, the quotient asks for the wires where k != 0)
+ *   COPY       pnp_check_witness with a wire map resident: slot (row i, wire j)
+ *              holds another value than the lowest slot, in (row, wire) order,
+ *              of its variable; the index is j.  Without a resident map copy
+ *              constraints are NOT checked (copy_checked = 0); an assignment
+ *              satisfies them by construction (copy_checked = 1, count 0).
+ * Returns PNP_OK (every constraint holds: the report is zero, first_row = ~0)
+ * or PNP_E_UNSAT (the report is filled and pnp_last_error names the first
+ * violation, e.g. "row 24: fixed_add constraint 2"); the report is the same on
+ * every run.  Synchronous, single GPU; every buffer it needs (the selector
+ * rows are forward transforms of the resident coefficients) is released
+ * before it returns, and no later proof is changed by it.  Afterwards, until
+ * the next proof, pnp_last_stage_times reports check_inputs, check_rows_ntt,
+ * check_rows, check_lookup, check_copy (ms); the row kernels are timed as
+ * "check_rows" (pnp_kernel_timing).
+ *   PNP_E_NOKEY  no prover key; pnp_check_assignment: no wire map resident
+ *   PNP_E_ARG    as the proving calls (domain, n_vars, public inputs), or a
+ *                context sharded over several ranks (as pnp_preprocess)
+ *   PNP_E_NOMEM  the scratch does not fit */
+#define PNP_E_UNSAT -6   /* the check ran; the witness violates the circuit (report filled) */
+
+enum { PNP_CHECK_ARITH = 0, PNP_CHECK_RANGE, PNP_CHECK_LOGIC, PNP_CHECK_FIXED_ADD,
+       PNP_CHECK_VAR_ADD, PNP_CHECK_LOOKUP, PNP_CHECK_COPY, PNP_CHECK_KINDS };
+
+typedef struct {
+    uint64_t violations;                 /* sum of by_kind */
+    uint64_t by_kind[PNP_CHECK_KINDS];   /* violated (row, constraint) pairs; COPY: slots */
+    uint64_t first_row;                  /* ~0 when none */
+    uint32_t first_kind, first_index;    /* of the least (row, kind, index), lexicographic */
+    uint32_t copy_checked;               /* 1: copy constraints checked, or hold by construction */
+    uint32_t reserved;
+} pnp_check_report;
+
+int pnp_check_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, int device_ptrs,
+                         uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
+                         pnp_check_report *report /* may be NULL */);
+int pnp_check_witness(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs,
+                      uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
+                      pnp_check_report *report /* may be NULL */);
 
 /* Per-stage wall-clock (ms) of the last pnp_prove, for the bench/profiles.
  * Writes up to `cap` doubles and their names; returns the stage count. */
@@ -666,6 +733,7 @@ static_assert(sizeof(ProverKeyC) == 44 * 8, "ProverKeyC layout (lib.rs:157-223)"
 static_assert(sizeof(CommitKeyC) == 16, "CommitKeyC layout (lib.rs:225-229)");
 static_assert(sizeof(pnp_verifier_key) == 8 + 96 + PNP_VK_POLYS * 96, "pnp_verifier_key layout (or_verifier_key)");
 static_assert(sizeof(pnp_circuit_desc) == 3 * 8 + (4 + 15 + 4) * 8, "pnp_circuit_desc layout");
+static_assert(sizeof(pnp_check_report) == (2 + PNP_CHECK_KINDS) * 8 + 4 * 4, "pnp_check_report layout");
 #else
 _Static_assert(sizeof(ProofC) == 2656, "ProofC layout (lib.rs:120-142)");
 _Static_assert(sizeof(ProverKeyC) == 44 * 8, "ProverKeyC layout (lib.rs:157-223)");

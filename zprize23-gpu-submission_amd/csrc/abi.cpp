@@ -1,7 +1,10 @@
 // abi.cpp — the extern "C" boundary (include/pnp_plonk.h): the v2 functions,
 // which return PNP_* codes and never exit.  What a context does behind them is
 // context.cpp, the proof prover.cpp, the prover-key loads prover_key.cpp; the
-// v1 gen_proof, which wraps them in the reference's contract, is v1.cpp.
+// v1 gen_proof, which wraps them in the reference's contract, is v1.cpp.  The
+// satisfiability check (pnp_check_assignment, pnp_check_witness) is whole
+// here, over the kernels of check.hip.
+#include <chrono>
 #include <memory>
 #include <stdlib.h>
 #include <string.h>
@@ -461,6 +464,245 @@ int pnp_prove_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, 
     ProveOpts o{n_pi, pi_pos, pi_canon, label ? label : "Merkle tree"};
     Assignment a{values, n_vars};
     PNP_TRY(prove_impl(ctx, nullptr, device_ptrs, out, &o, &a));
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- satisfiability check
+namespace {
+
+const char *const kCheckKindName[PNP_CHECK_KINDS] = {"arith", "range", "logic", "fixed_add",
+                                                    "var_add", "lookup", "copy"};
+
+// One check in flight (pnp_check_assignment, pnp_check_witness).  Every device
+// buffer is a member or a local of check_columns: all of it is released when
+// the call returns, whatever way it returns.
+struct Check {
+    pnp_ctx *const ctx;
+    const pnp::ProveOpts opt;
+    pnp_check_report *const report;
+    pnp::ProveDomain dom;
+    hipStream_t s = nullptr;
+    std::vector<uint64_t> pi_pos;
+    std::vector<Fr> pi_val;
+    pnp::DevBuf col[4];  // the padded witness columns, D rows each
+    std::chrono::steady_clock::time_point t0;
+
+    Check(pnp_ctx *c, uint64_t n_pi, const uint64_t *pos, const uint64_t *canon, pnp_check_report *r)
+        : ctx(c), opt{n_pi, pos, canon, nullptr}, report(r) {}
+
+    void mark(const char *name) {
+        PNP_HIP(hipStreamSynchronize(s));
+        const auto t1 = std::chrono::steady_clock::now();
+        ctx->stages.emplace_back(name, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    }
+
+    // the prologue pnp_prove_ex / pnp_prove_assignment run (prove_domain,
+    // public_input_map), without a commit key; single GPU
+    void begin(const CircuitC *cs, const pnp::Assignment *asg) {
+        if (report) {
+            memset(report, 0, sizeof *report);
+            report->first_row = ~0ULL;
+        }
+        if (ctx->msm.world > 1) {
+            set_error("check: the context is sharded over %d ranks (a multi-rank check is not supported)",
+                      ctx->msm.world);
+            throw pnp::Error(PNP_E_ARG);
+        }
+        dom = pnp::prove_domain(ctx, cs, asg, false);
+        pnp::public_input_map(opt, dom.n, pi_pos, pi_val);
+        tables_wait(ctx);  // (the NTT tables are shared with a background build)
+        PNP_HIP(hipSetDevice(ctx->device));
+        s = ctx->stream;
+        ctx->stages.clear();
+        t0 = std::chrono::steady_clock::now();
+        for (auto &c : col) c.alloc(32 * dom.n);
+    }
+
+    void check_columns(const uint64_t *s_rows, uint64_t s_n, bool copy_over_map, uint32_t copy_checked);
+};
+
+// The common part: the witness is in col[] (padded), s_rows are the caller's
+// q_lookup rows (the first s_n; nullptr: a zero column).
+void Check::check_columns(const uint64_t *s_rows, uint64_t s_n, bool copy_over_map, uint32_t copy_checked) {
+    using namespace pnp;
+    const ResidentKey &key = ctx->key;
+    const uint64_t D = dom.n;
+    const uint32_t lg = dom.lg;
+    mark("check_inputs");
+
+    // the selector rows: forward transforms of the resident coefficients, of
+    // the selectors this key has, into scratch
+    DevBuf rows[kKeyRows];
+    const uint64_t *const *coeffs = reinterpret_cast<const uint64_t *const *>(&key.dev);
+    auto row_values = [&](KeyPoly r) -> const uint64_t * {
+        if (!key.has(r)) return nullptr;
+        rows[r].alloc(32 * D);
+        ntt_run(ctx->ntt, rows[r].u64(), lg, false, false, s, coeffs[kKeyTable[r].coeffs]);
+        return rows[r].u64();
+    };
+    CheckRows r{};
+    for (int j = 0; j < 4; j++) r.w[j] = col[j].u64();
+    r.q_m = row_values(kQm), r.q_l = row_values(kQl), r.q_r = row_values(kQr), r.q_o = row_values(kQo);
+    r.q_4 = row_values(kQ4), r.q_c = row_values(kQc), r.q_hl = row_values(kQhl), r.q_hr = row_values(kQhr);
+    r.q_h4 = row_values(kQh4), r.q_arith = row_values(kQarith);
+    for (int f = 0; f < 4; f++) r.fam[f] = row_values(KeyPoly(kRange + f));
+    // the key's q_lookup rows: the resident wire map keeps them
+    const uint64_t *k_rows = key.wm_qlk.p ? key.wm_qlk.u64() : row_values(kQlookup);
+    // the public inputs: ascending rows, Montgomery values
+    DevBuf pis;
+    r.n_pi = (uint32_t)pi_pos.size();
+    r.lg = lg;
+    if (r.n_pi) {
+        // (the values start 16-byte aligned: an even count of words before them)
+        const size_t val_off = (pi_pos.size() + 1) & ~size_t(1);
+        std::vector<uint64_t> packed(val_off + 4 * pi_pos.size());
+        for (size_t k = 0; k < pi_pos.size(); k++) {
+            packed[k] = pi_pos[k];
+            to_u64_limbs(pi_val[k], &packed[val_off + 4 * k]);
+        }
+        pis.alloc(8 * packed.size());
+        PNP_HIP(hipMemcpyAsync(pis.p, packed.data(), 8 * packed.size(), hipMemcpyHostToDevice, s));
+        PNP_HIP(hipStreamSynchronize(s));
+        r.pi_pos = pis.u64();
+        r.pi_val = pis.u64() + val_off;
+    }
+    DevBuf recbuf(sizeof(CheckRecord));
+    CheckRecord *rec = static_cast<CheckRecord *>(recbuf.p);
+    k_check_reset(rec, s);
+    mark("check_rows_ntt");
+
+    // the gates: arithmetic + PI on every row; a custom family only when the key has it
+    int arith_cols = 4;
+    for (const uint64_t *p : {r.q_m, r.q_l, r.q_r, r.q_o, r.q_4, r.q_c, r.q_hl, r.q_hr, r.q_h4, r.q_arith})
+        arith_cols += p != nullptr;
+    int fam_cols = 0;
+    hipEvent_t e0 = nullptr;
+    ctx->ktimer.begin("check_rows", s, e0);
+    k_check_arith(r, rec, s);
+    for (int f = 0; f < 4; f++) {
+        if (!r.fam[f]) continue;
+        k_check_family(f, r, rec, s);
+        fam_cols++;  // its selector column; the wires only where it is non-zero
+    }
+    ctx->ktimer.end("check_rows", s, e0, 32.0 * (double)D * (arith_cols + fam_cols));
+    mark("check_rows");
+
+    // the lookup: nothing to do when neither the caller nor the key selects a row
+    if (s_rows || k_rows) {
+        const uint64_t *t[4] = {key.dev.table1, key.dev.table2, key.dev.table3, key.dev.table4};
+        DevBuf slots(8 * D);
+        k_check_table_set(t, lg, slots.u32(), s);
+        const uint64_t *w[4] = {r.w[0], r.w[1], r.w[2], r.w[3]};
+        k_check_lookup(w, s_rows, s_n, k_rows, t, slots.u32(), lg, rec, s);
+        PNP_HIP(hipStreamSynchronize(s));  // (slots is released here)
+    }
+    mark("check_lookup");
+
+    if (copy_over_map) {
+        DevBuf first(4 * key.wm_vars);
+        const uint32_t *var = key.wm_var.u32();
+        const uint64_t ng = key.wm_gates;
+        const uint32_t *dvar[4] = {var, var + ng, var + 2 * ng, var + 3 * ng};
+        const uint64_t *w[4] = {r.w[0], r.w[1], r.w[2], r.w[3]};
+        k_check_copy(dvar, ng, key.wm_vars, w, lg, first.u32(), rec, s);
+        PNP_HIP(hipStreamSynchronize(s));
+    }
+    mark("check_copy");
+
+    CheckRecord h;
+    PNP_HIP(hipMemcpyAsync(&h, rec, sizeof h, hipMemcpyDeviceToHost, s));
+    PNP_HIP(hipStreamSynchronize(s));
+    ctx->ktimer.collect();
+    pnp_check_report rep;
+    memset(&rep, 0, sizeof rep);
+    rep.first_row = ~0ULL;
+    rep.copy_checked = copy_checked;
+    for (int k = 0; k < PNP_CHECK_KINDS; k++) {
+        rep.by_kind[k] = h.by_kind[k];
+        rep.violations += h.by_kind[k];
+    }
+    if (rep.violations) {
+        rep.first_row = h.first >> 8;
+        rep.first_kind = (uint32_t)(h.first >> 4) & 15;
+        rep.first_index = (uint32_t)h.first & 15;
+    }
+    if (report) *report = rep;
+    if (rep.violations) {
+        set_error("row %llu: %s constraint %u (%llu violations)", (unsigned long long)rep.first_row,
+                  kCheckKindName[rep.first_kind], rep.first_index, (unsigned long long)rep.violations);
+        throw Error(PNP_E_UNSAT);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnp_check_assignment(pnp_ctx *ctx, const uint64_t *values, uint64_t n_vars, int device_ptrs, uint64_t n_pi,
+                         const uint64_t *pi_pos, const uint64_t *pi_canon, pnp_check_report *report) {
+    if (!ctx || !values || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
+    if (device_ptrs && ((uintptr_t)values & 15)) {
+        set_error("check assignment: HBM values must be 16-byte aligned");
+        return PNP_E_ARG;
+    }
+    PNP_TRY({
+        Check c(ctx, n_pi, pi_pos, pi_canon, report);
+        const Assignment a{values, n_vars};
+        c.begin(nullptr, &a);
+        // the columns through the resident wire map (assignment.hip), as the prover gathers them
+        pnp::DevBuf up;
+        const uint64_t *vals = values;
+        if (!device_ptrs) {
+            up.alloc(32 * n_vars);
+            h2d_batch(ctx, {{up.p, values, 32 * n_vars}});
+            vals = up.u64();
+        }
+        const uint64_t ng = c.dom.ng;
+        const uint32_t *var = ctx->key.wm_var.u32();
+        const uint32_t *dvar[4] = {var, var + ng, var + 2 * ng, var + 3 * ng};
+        uint64_t *w[4] = {c.col[0].u64(), c.col[1].u64(), c.col[2].u64(), c.col[3].u64()};
+        pnp::k_gather_witness(dvar, ng, vals, n_vars, c.dom.lg, w, c.s);
+        PNP_HIP(hipStreamSynchronize(c.s));
+        up.release();
+        // s = k: the key's q_lookup rows, as pnp_prove_assignment; one value a
+        // variable: the copy constraints hold by construction
+        const uint64_t *k_rows = ctx->key.wm_qlk.p ? ctx->key.wm_qlk.u64() : nullptr;
+        c.check_columns(k_rows, c.dom.n, false, 1);
+    });
+}
+
+int pnp_check_witness(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t n_pi, const uint64_t *pi_pos,
+                      const uint64_t *pi_canon, pnp_check_report *report) {
+    if (!ctx || !cs || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
+    if (cs->n && (!cs->w_l || !cs->w_r || !cs->w_o || !cs->w_4)) return PNP_E_ARG;
+    PNP_TRY({
+        Check c(ctx, n_pi, pi_pos, pi_canon, report);
+        c.begin(cs, nullptr);
+        // the padded columns and the caller's q_lookup rows, staged as pnp_prove_ex stages them
+        const uint64_t ng = c.dom.ng, D = c.dom.n;
+        const uint64_t *wsrc[4] = {cs->w_l, cs->w_r, cs->w_o, cs->w_4};
+        pnp::DevBuf qlk;
+        std::vector<H2D> up;
+        for (int j = 0; j < 4; j++) {
+            uint64_t *dst = c.col[j].u64();
+            if (device_ptrs) PNP_HIP(hipMemcpyAsync(dst, wsrc[j], 32 * ng, hipMemcpyDeviceToDevice, c.s));
+            else up.push_back({dst, wsrc[j], 32 * ng});
+            if (D > ng) PNP_HIP(hipMemsetAsync(dst + 4 * ng, 0, 32 * (D - ng), c.s));
+        }
+        const uint64_t *s_rows = nullptr;
+        if (cs->q_lookup && ng) {
+            qlk.alloc(32 * ng);
+            if (device_ptrs) PNP_HIP(hipMemcpyAsync(qlk.p, cs->q_lookup, 32 * ng, hipMemcpyDeviceToDevice, c.s));
+            else up.push_back({qlk.p, cs->q_lookup, 32 * ng});
+            s_rows = qlk.u64();
+        }
+        if (!up.empty()) h2d_batch(ctx, up);
+        // with a wire map resident the columns are checked against it
+        const bool map = ctx->key.wm_loaded;
+        c.check_columns(s_rows, ng, map, map ? 1 : 0);
+    });
 }
 
 int pnp_last_stage_times(pnp_ctx *ctx, double *ms, const char **names, int cap) {

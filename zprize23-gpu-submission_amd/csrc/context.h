@@ -206,6 +206,18 @@ struct Assignment {
     const uint64_t *values;
     uint64_t n_vars;
 };
+// What a proof and a satisfiability check (abi.cpp pnp_check_*) decide alike
+// before any work (prover.cpp).  prove_domain: the keys are loaded (the commit
+// key only with need_ck), an assignment has its wire map and variable count,
+// and the domain n = 2^lg of the inputs is the resident key's; ng = the gate
+// rows.  public_input_map: the public inputs of `opt` in BTreeMap order,
+// zero values dropped, Montgomery; positions distinct and < n.  Both throw Error.
+struct ProveDomain {
+    uint64_t n = 1, ng = 0;
+    uint32_t lg = 0;
+};
+ProveDomain prove_domain(pnp_ctx *ctx, const CircuitC *cs, const Assignment *asg, bool need_ck);
+void public_input_map(const ProveOpts &opt, uint64_t n, std::vector<uint64_t> &pos, std::vector<Fr> &val);
 // The witness comes from the columns of `cs`, or, with `asg` (then cs is
 // nullptr and opt is given), from the assignment: the domain is the resident
 // key's, the gates and q_lookup rows the resident wire map's.  Throws Error.

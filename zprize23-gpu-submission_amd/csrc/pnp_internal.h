@@ -317,6 +317,40 @@ void k_gather_witness(const uint32_t *const d_var[4], uint64_t n_gates, const ui
 // each) differ, ~0 when they are equal.  Synchronous; scratch: 8 bytes
 uint64_t k_first_diff4(const uint64_t *const a[4], const uint64_t *const b[4], uint32_t lg, DevBuf &scratch,
                        hipStream_t s);
+// ---- the satisfiability check of a witness, row by row (check.hip) ----
+// what the kernels leave behind: the least violated (row << 8 | kind << 4 |
+// index), ~0 when none, and the violated (row, constraint) pairs per kind
+struct CheckRecord {
+    unsigned long long first;
+    unsigned long long by_kind[PNP_CHECK_KINDS];
+};
+// the rows the gate kernels read: D = 2^lg rows each, HBM, 16-byte aligned
+struct CheckRows {
+    const uint64_t *w[4];  // the padded witness columns (zero from row n_gates on)
+    const uint64_t *q_m, *q_l, *q_r, *q_o, *q_4, *q_c, *q_hl, *q_hr, *q_h4, *q_arith;  // q_m: nullptr = zero
+    const uint64_t *fam[4];   // range, logic, fixed-base, curve-add selector rows; nullptr = absent
+    const uint64_t *pi_pos;   // n_pi ascending rows and their Montgomery values (nullptr with n_pi = 0)
+    const uint64_t *pi_val;
+    uint32_t n_pi, lg;
+};
+void k_check_reset(CheckRecord *rec, hipStream_t s);
+// ARITH, constraint 0, on every row
+void k_check_arith(const CheckRows &r, CheckRecord *rec, hipStream_t s);
+// family f (0 range .. 3 curve-add, r.fam[f] != nullptr), its own kernel
+void k_check_family(int f, const CheckRows &r, CheckRecord *rec, hipStream_t s);
+// the set of the distinct rows of the table t[0..3] (D rows each): row indices
+// in `slots` (2 D u32, open addressing); rows equal to row 0 stay out but row 0
+void k_check_table_set(const uint64_t *const t[4], uint32_t lg, uint32_t *slots, hipStream_t s);
+// LOOKUP: s_rows (the first s_n rows read, zero beyond; nullptr = zero), k_rows
+// (D rows; nullptr = zero) as include/pnp_plonk.h states it
+void k_check_lookup(const uint64_t *const w[4], const uint64_t *s_rows, uint64_t s_n, const uint64_t *k_rows,
+                    const uint64_t *const t[4], const uint32_t *slots, uint32_t lg, CheckRecord *rec, hipStream_t s);
+// COPY: every slot of the wire map against the lowest slot of its variable;
+// first: n_vars u32 of scratch.  An id >= n_vars (the loaders refuse such
+// maps) is skipped
+void k_check_copy(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const uint64_t *const w[4],
+                  uint32_t lg, uint32_t *first, CheckRecord *rec, hipStream_t s);
+
 void k_synth_merkle(int height, const uint64_t *pc_mont_host, const uint64_t *leaves, const uint64_t *blind,
                     uint64_t *nodes, uint64_t *const w[4], uint64_t *const sel[9], uint64_t *const sigma[4],
                     uint64_t n, hipStream_t s);

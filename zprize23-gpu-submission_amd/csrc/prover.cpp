@@ -118,6 +118,54 @@ template <class... A>
     throw Error(code);
 }
 
+}  // namespace
+
+// the keys, the assignment and the domain: the circuit's, which must be the
+// key's; an assignment is proved (checked) on the key's (its wire map was
+// loaded against it)
+ProveDomain prove_domain(pnp_ctx *ctx, const CircuitC *cs, const Assignment *asg, bool need_ck) {
+    if (!ctx->key.loaded || (need_ck && !ctx->ck_loaded))
+        fail(PNP_E_NOKEY, need_ck ? "prover key / commit key not loaded" : "prover key not loaded");
+    if (asg) {
+        if (!ctx->key.wm_loaded)
+            fail(PNP_E_NOKEY, "no wire map resident (pnp_preprocess or pnp_load_wire_map first)");
+        if (asg->n_vars != ctx->key.wm_vars)
+            fail(PNP_E_ARG, "assignment of %llu variables, the resident wire map has %llu",
+                 (unsigned long long)asg->n_vars, (unsigned long long)ctx->key.wm_vars);
+    }
+    ProveDomain d;
+    const uint64_t bound = asg ? ctx->key.n : cs->n > cs->lookup_len ? cs->n : cs->lookup_len;
+    while (d.n < bound) { d.n <<= 1; d.lg++; }
+    if (d.n != ctx->key.n)
+        fail(PNP_E_ARG, "circuit domain %llu != prover key domain %llu", (unsigned long long)d.n,
+             (unsigned long long)ctx->key.n);
+    if (need_ck && ctx->ck_points < d.n)
+        fail(PNP_E_ARG, "commit key has %llu points, need %llu", (unsigned long long)ctx->ck_points,
+             (unsigned long long)d.n);
+    d.ng = asg ? ctx->key.wm_gates : cs->n;
+    return d;
+}
+
+// a PublicInputs map (pi.rs:16-86): BTreeMap order, zero values dropped, Montgomery
+void public_input_map(const ProveOpts &opt, uint64_t n, std::vector<uint64_t> &pos, std::vector<Fr> &val) {
+    std::vector<std::pair<uint64_t, Fr>> v;
+    for (uint64_t k = 0; k < opt.n_pi; k++) {
+        if (opt.pi_pos[k] >= n)
+            fail(PNP_E_ARG, "public input position %llu out of range", (unsigned long long)opt.pi_pos[k]);
+        v.emplace_back(opt.pi_pos[k], to_mont(from_u64_limbs<FrP>(opt.pi_canon + 4 * k)));
+    }
+    std::sort(v.begin(), v.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    for (size_t k = 0; k < v.size(); k++) {
+        if (k && v[k].first == v[k - 1].first)
+            fail(PNP_E_ARG, "public input position %llu given twice", (unsigned long long)v[k].first);
+        if (v[k].second.is_zero()) continue;
+        pos.push_back(v[k].first);
+        val.push_back(v[k].second);
+    }
+}
+
+namespace {
+
 // Round 5's evaluations (Montgomery).  kEvalTable below is their one list:
 // where each goes in the proof and under which label into the transcript.
 struct Evals {
@@ -254,29 +302,13 @@ struct Proof {
     bool round5_linearise(int nbq);
 };
 
-// the keys, the assignment and the domain: the circuit's, which must be the
-// key's; an assignment is proved on the key's (its wire map was loaded against it)
+// the keys and the domain (prove_domain), the output and the stream
 void Proof::check_and_size() {
-    if (!ctx->key.loaded || !ctx->ck_loaded) fail(PNP_E_NOKEY, "prover key / commit key not loaded");
-    if (asg) {
-        if (!ctx->key.wm_loaded)
-            fail(PNP_E_NOKEY, "no wire map resident (pnp_preprocess or pnp_load_wire_map first)");
-        if (asg->n_vars != ctx->key.wm_vars)
-            fail(PNP_E_ARG, "assignment of %llu variables, the resident wire map has %llu",
-                 (unsigned long long)asg->n_vars, (unsigned long long)ctx->key.wm_vars);
-    }
+    const ProveDomain dom = prove_domain(ctx, cs, asg, true);
     memset(out, 0, sizeof *out);
     s = ctx->stream;
     PNP_HIP(hipSetDevice(ctx->device));
-    uint64_t bound = asg ? ctx->key.n : cs->n > cs->lookup_len ? cs->n : cs->lookup_len;
-    while (n < bound) { n <<= 1; lg++; }
-    if (n != ctx->key.n)
-        fail(PNP_E_ARG, "circuit domain %llu != prover key domain %llu", (unsigned long long)n,
-             (unsigned long long)ctx->key.n);
-    if (ctx->ck_points < n)
-        fail(PNP_E_ARG, "commit key has %llu points, need %llu", (unsigned long long)ctx->ck_points,
-             (unsigned long long)n);
-    ng = asg ? ctx->key.wm_gates : cs->n;
+    n = dom.n, lg = dom.lg, ng = dom.ng;
 }
 
 // public inputs: v1 = the circuit's one (pi, intended_pi_pos), appended as
@@ -291,20 +323,7 @@ void Proof::public_inputs() {
         tr.append_pi("pi", cs->pi, cs->intended_pi_pos);
         return;
     }
-    std::vector<std::pair<uint64_t, Fr>> v;
-    for (uint64_t k = 0; k < opt->n_pi; k++) {
-        if (opt->pi_pos[k] >= n)
-            fail(PNP_E_ARG, "public input position %llu out of range", (unsigned long long)opt->pi_pos[k]);
-        v.emplace_back(opt->pi_pos[k], to_mont(from_u64_limbs<FrP>(opt->pi_canon + 4 * k)));
-    }
-    std::sort(v.begin(), v.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
-    for (size_t k = 0; k < v.size(); k++) {
-        if (k && v[k].first == v[k - 1].first)
-            fail(PNP_E_ARG, "public input position %llu given twice", (unsigned long long)v[k].first);
-        if (v[k].second.is_zero()) continue;
-        pi_pos.push_back(v[k].first);
-        pi_val.push_back(v[k].second);
-    }
+    public_input_map(*opt, n, pi_pos, pi_val);
     std::vector<uint64_t> canon(4 * pi_val.size());
     for (size_t k = 0; k < pi_val.size(); k++) to_u64_limbs(from_mont(pi_val[k]), &canon[4 * k]);
     tr.append_pis("pi", pi_pos.size(), pi_pos.data(), canon.data());

@@ -40,13 +40,36 @@ PNP_HD Fr gate_delta(const Fr &f) {
     return f * f1 * f2 * f3;
 }
 
-// Range::constraints (widget/range.rs:44-60)
+// The constraints of one family, each on its own: c_*(w, emit) hands
+// constraint k of the family, without its power of the separation challenge,
+// to emit(CIdx<k>{}, value), in the widget's order.  The row-by-row
+// satisfiability check (check.hip) tests each value against zero; w_* below,
+// what the quotient and the linearisation use, are their kappa-weighted sums,
+// taken as the values arrive (no value is kept).
+template <int K>
+struct CIdx {
+    static constexpr int value = K;
+};
+constexpr int kRangeConstraints = 4, kLogicConstraints = 5, kFbsmConstraints = 4, kCaddConstraints = 3;
+
+// Range (widget/range.rs:44-60)
+template <class Emit>
+PNP_HD void c_range(const WidgetVals &w, Emit &&emit) {
+    emit(CIdx<0>{}, gate_delta(w.c - mul4(w.d)));
+    emit(CIdx<1>{}, gate_delta(w.b - mul4(w.c)));
+    emit(CIdx<2>{}, gate_delta(w.a - mul4(w.b)));
+    emit(CIdx<3>{}, gate_delta(w.d_next - mul4(w.a)));
+}
+
+// Range::constraints
 PNP_HD Fr w_range(const Fr &sep, const WidgetVals &w) {
     const Fr kappa = sep * sep, kappa2 = kappa * kappa, kappa3 = kappa2 * kappa;
-    Fr acc = gate_delta(w.c - mul4(w.d));
-    acc += gate_delta(w.b - mul4(w.c)) * kappa;
-    acc += gate_delta(w.a - mul4(w.b)) * kappa2;
-    acc += gate_delta(w.d_next - mul4(w.a)) * kappa3;
+    Fr acc = Fr::zero();
+    c_range(w, [&](auto k, const Fr &v) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K == 0) acc = v;
+        else acc += v * (K == 1 ? kappa : K == 2 ? kappa2 : kappa3);
+    });
     return acc * sep;
 }
 
@@ -63,44 +86,78 @@ PNP_HD Fr delta_xor_and(const Fr &a, const Fr &b, const Fr &w, const Fr &c, cons
     return B + E;
 }
 
-// Logic::constraints (widget/logic.rs:59-82)
+// Logic (widget/logic.rs:59-82)
+template <class Emit>
+PNP_HD void c_logic(const WidgetVals &w, Emit &&emit) {
+    const Fr a = w.a_next - mul4(w.a), b = w.b_next - mul4(w.b), d = w.d_next - mul4(w.d);
+    emit(CIdx<0>{}, gate_delta(a));
+    emit(CIdx<1>{}, gate_delta(b));
+    emit(CIdx<2>{}, gate_delta(d));
+    emit(CIdx<3>{}, w.c - a * b);
+    emit(CIdx<4>{}, delta_xor_and(a, b, w.c, d, w.q_c));
+}
+
+// Logic::constraints
 PNP_HD Fr w_logic(const Fr &sep, const WidgetVals &w) {
     const Fr kappa = sep * sep, kappa2 = kappa * kappa, kappa3 = kappa2 * kappa, kappa4 = kappa3 * kappa;
-    const Fr a = w.a_next - mul4(w.a), b = w.b_next - mul4(w.b), d = w.d_next - mul4(w.d);
-    Fr acc = gate_delta(a);
-    acc += gate_delta(b) * kappa;
-    acc += gate_delta(d) * kappa2;
-    acc += (w.c - a * b) * kappa3;
-    acc += delta_xor_and(a, b, w.c, d, w.q_c) * kappa4;
+    Fr acc = Fr::zero();
+    c_logic(w, [&](auto k, const Fr &v) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K == 0) acc = v;
+        else acc += v * (K == 1 ? kappa : K == 2 ? kappa2 : K == 3 ? kappa3 : kappa4);
+    });
     return acc * sep;
 }
 
-// FixedBaseScalarMul::constraints (widget/ecc/fixed_base_scalar_mul.rs:89-155)
-PNP_HD Fr w_fbsm(const Fr &sep, const WidgetVals &w) {
+// FixedBaseScalarMul (widget/ecc/fixed_base_scalar_mul.rs:89-155): bit
+// consistency, xy_alpha, the x and the y equation
+template <class Emit>
+PNP_HD void c_fbsm(const WidgetVals &w, Emit &&emit) {
     const Fr one = Fr::one();
-    const Fr kappa = sep * sep, kappa2 = kappa * kappa, kappa3 = kappa2 * kappa;
     const Fr bit = w.d_next - dbl(w.d);                   // extract_bit
-    const Fr bit_c = bit * (bit - one) * (bit + one);     // check_bit_consistency
+    emit(CIdx<0>{}, bit * (bit - one) * (bit + one));     // check_bit_consistency
     const Fr y_alpha = bit * bit * (w.q_r - one) + one;   // y_beta = q_r
     const Fr x_alpha = w.q_l * bit;                       // x_beta = q_l
-    const Fr xy_c = (bit * w.q_c - w.c) * kappa;          // xy_alpha = c
+    emit(CIdx<1>{}, bit * w.q_c - w.c);                   // xy_alpha = c
     const Fr m = w.c * w.a * w.b * jj_coeff_d();          // xy_alpha acc_x acc_y D
-    const Fr x_c = (w.a_next + w.a_next * m - (x_alpha * w.b + y_alpha * w.a)) * kappa2;
-    const Fr y_c = (w.b_next - w.b_next * m - (y_alpha * w.b - jj_coeff_a() * x_alpha * w.a)) * kappa3;
-    return (bit_c + x_c + y_c + xy_c) * sep;
+    emit(CIdx<2>{}, w.a_next + w.a_next * m - (x_alpha * w.b + y_alpha * w.a));
+    emit(CIdx<3>{}, w.b_next - w.b_next * m - (y_alpha * w.b - jj_coeff_a() * x_alpha * w.a));
 }
 
-// CurveAddition::constraints (widget/ecc/curve_addition.rs:61-96)
-PNP_HD Fr w_cadd(const Fr &sep, const WidgetVals &w) {
+// FixedBaseScalarMul::constraints
+PNP_HD Fr w_fbsm(const Fr &sep, const WidgetVals &w) {
+    const Fr kappa = sep * sep, kappa2 = kappa * kappa, kappa3 = kappa2 * kappa;
+    Fr acc = Fr::zero();
+    c_fbsm(w, [&](auto k, const Fr &v) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K == 0) acc = v;
+        else acc += v * (K == 1 ? kappa : K == 2 ? kappa2 : kappa3);
+    });
+    return acc * sep;
+}
+
+// CurveAddition (widget/ecc/curve_addition.rs:61-96): x1 y2, the x3 and the y3 equation
+template <class Emit>
+PNP_HD void c_cadd(const WidgetVals &w, Emit &&emit) {
     const Fr &x1 = w.a, &y1 = w.b, &x2 = w.c, &y2 = w.d, &x3 = w.a_next, &y3 = w.b_next,
              &x1y2 = w.d_next;
-    const Fr kappa = sep * sep;
-    const Fr xy_c = x1 * y2 - x1y2;
+    emit(CIdx<0>{}, x1 * y2 - x1y2);
     const Fr y1x2 = y1 * x2, y1y2 = y1 * y2, x1x2 = x1 * x2;
     const Fr dm = jj_coeff_d() * x1y2 * y1x2;
-    const Fr x3_c = (x1y2 + y1x2 - (x3 + x3 * dm)) * kappa;
-    const Fr y3_c = (y1y2 - jj_coeff_a() * x1x2 - (y3 - y3 * dm)) * (kappa * kappa);
-    return (xy_c + x3_c + y3_c) * sep;
+    emit(CIdx<1>{}, x1y2 + y1x2 - (x3 + x3 * dm));
+    emit(CIdx<2>{}, y1y2 - jj_coeff_a() * x1x2 - (y3 - y3 * dm));
+}
+
+// CurveAddition::constraints
+PNP_HD Fr w_cadd(const Fr &sep, const WidgetVals &w) {
+    const Fr kappa = sep * sep;
+    Fr acc = Fr::zero();
+    c_cadd(w, [&](auto k, const Fr &v) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K == 0) acc = v;
+        else acc += v * (K == 1 ? kappa : kappa * kappa);
+    });
+    return acc * sep;
 }
 
 }  // namespace pnp

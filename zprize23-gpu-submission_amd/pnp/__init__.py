@@ -23,7 +23,7 @@ _LIB = None
 
 PNP_OK = 0
 ERRORS = {-1: "PNP_E_ARG", -2: "PNP_E_DEVICE", -3: "PNP_E_NOKEY", -4: "PNP_E_ENVELOPE",
-          -5: "PNP_E_NOMEM"}
+          -5: "PNP_E_NOMEM", -6: "PNP_E_UNSAT"}
 
 # exported symbols declared by include/pnp_plonk.h (checked by tests/test_abi.py)
 SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
@@ -38,7 +38,8 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_set_exchange_v", "pnp_commit_segments", "pnp_hbm_usage",
            "pnp_ctx_stream", "pnp_set_exchange_ordered", "pnp_v1_context",
            "pnp_preprocess", "pnp_wire_sigma",
-           "pnp_load_wire_map", "pnp_gather_witness", "pnp_prove_assignment")
+           "pnp_load_wire_map", "pnp_gather_witness", "pnp_prove_assignment",
+           "pnp_check_assignment", "pnp_check_witness")
 
 
 # int allgather(void *user, uint64_t bytes_per_rank) — pnp_set_msm_shard
@@ -85,7 +86,7 @@ def load(path: str = LIB_PATH):
     lib.pnp_prove.argtypes = [vp, C.POINTER(abi.CircuitC), i32, C.POINTER(abi.ProofC)]
     lib.pnp_prove_ex.argtypes = [vp, C.POINTER(abi.CircuitC), i32, u64, vp, vp, C.c_char_p,
                                  C.POINTER(abi.ProofC)]
-    for name, argtypes in abi.ASSIGNMENT_ARGTYPES.items():
+    for name, argtypes in list(abi.ASSIGNMENT_ARGTYPES.items()) + list(abi.CHECK_ARGTYPES.items()):
         getattr(lib, name).argtypes = argtypes
     lib.pnp_last_stage_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_char_p), i32]
     lib.pnp_kernel_timing.argtypes = [vp, i32]
@@ -243,6 +244,44 @@ class Context:
                                             C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p), label,
                                             C.byref(out)), "pnp_prove_assignment")
         return out
+
+    @staticmethod
+    def _pi_args(pis):
+        k = len(pis)
+        pos = (C.c_uint64 * max(k, 1))(*[p for p, _ in pis])
+        vals = (C.c_uint64 * max(4 * k, 1))()
+        for i, (_, v) in enumerate(pis):
+            for j in range(4):
+                vals[4 * i + j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+        return k, pos, vals
+
+    def _checked(self, rc: int, report: abi.CheckReport, what: str):
+        if rc != abi.PNP_E_UNSAT:
+            check(rc, what)
+        return rc == PNP_OK, report
+
+    def check_assignment(self, values: int, n_vars: int, device_ptrs: bool, pis):
+        """pnp_check_assignment: does the assignment (values as
+        prove_assignment) satisfy the resident key's circuit?  Returns (ok,
+        abi.CheckReport); raises on every error but PNP_E_UNSAT."""
+        k, pos, vals = self._pi_args(pis)
+        rep = abi.CheckReport()
+        rc = self.lib.pnp_check_assignment(self.h, C.c_void_p(values), n_vars, int(device_ptrs), k,
+                                           C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p), C.byref(rep))
+        return self._checked(rc, rep, "pnp_check_assignment")
+
+    def check_witness(self, cs: abi.CircuitC, device_ptrs: bool, pis):
+        """pnp_check_witness: the same for witness columns (cs as prove_ex);
+        with a wire map resident the copy constraints are checked too."""
+        k, pos, vals = self._pi_args(pis)
+        rep = abi.CheckReport()
+        rc = self.lib.pnp_check_witness(self.h, C.byref(cs), int(device_ptrs), k, C.cast(pos, C.c_void_p),
+                                        C.cast(vals, C.c_void_p), C.byref(rep))
+        return self._checked(rc, rep, "pnp_check_witness")
+
+    def last_error(self) -> str:
+        msg = self.lib.pnp_last_error()
+        return msg.decode() if msg else ""
 
     def stage_times(self):
         cap = 64

@@ -133,6 +133,30 @@ ASSIGNMENT_ARGTYPES = {
                              C.c_char_p, C.POINTER(ProofC)],
 }
 
+# The satisfiability check (pnp_check_assignment, pnp_check_witness).
+PNP_E_UNSAT = -6
+CHECK_KINDS = ("arith", "range", "logic", "fixed_add", "var_add", "lookup", "copy")
+
+
+class CheckReport(C.Structure):
+    """pnp_check_report: violated (row, constraint) pairs by kind (CHECK_KINDS
+    order; copy: slots), their sum, and the least (row, kind, index);
+    first_row = 2^64 - 1 when nothing is violated."""
+    _fields_ = [("violations", C.c_uint64), ("by_kind", C.c_uint64 * len(CHECK_KINDS)),
+                ("first_row", C.c_uint64), ("first_kind", C.c_uint32), ("first_index", C.c_uint32),
+                ("copy_checked", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+#   pnp_check_assignment(ctx, values, n_vars, device_ptrs, n_pi, pi_pos, pi_canon, report)
+#   pnp_check_witness(ctx, cs, device_ptrs, n_pi, pi_pos, pi_canon, report)
+CHECK_ARGTYPES = {
+    "pnp_check_assignment": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                             C.POINTER(CheckReport)],
+    "pnp_check_witness": [C.c_void_p, C.POINTER(CircuitC), C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                          C.POINTER(CheckReport)],
+}
+
+assert C.sizeof(CheckReport) == (2 + len(CHECK_KINDS)) * 8 + 16
 assert C.sizeof(VerifierKey) == 8 + 96 + 23 * 96
 assert C.sizeof(CircuitDesc) == 3 * 8 + (4 + 15 + 4) * 8
 assert C.sizeof(ProofC) == 2656
