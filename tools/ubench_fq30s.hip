@@ -17,6 +17,12 @@
 // sum is named in an assumption (mad()).  k_mul30s<C> times the plain product,
 // k_mix30s<C> the mix of one mixed addition (6 products, 2 squares, one
 // a b + c d with one reduction).
+//
+// FOLD (k_madd30s<C, F>): the whole mixed addition, products and subtractions.
+// F = 0: the three subtractions from a fresh product (U2 - X, S2 - Y,
+// R^2 - PPP - 2 Q) limb-wise with the carries renormalised; F = 1: folded into
+// that product's reduction, one multiply-add a limb (mul_sub, sqr_sub2).  The
+// two give the same limbs, which check() compares on the host.
 //   hipcc -O3 --offload-arch=gfx950 -I<csrc> ubench_fq30s.hip -o ubench_fq30s
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -129,6 +135,88 @@ __host__ __device__ __forceinline__ F30 mul2(const F30 &a, const F30 &b, const F
     r.l[12] = (int32_t)acc;
     return r;
 }
+// ---- the subtractions of the mixed addition (field30s.cuh), and the FOLD of
+// the three that follow a fresh product into that product's reduction: limb j
+// of the subtrahend goes into result column 13 + j, times an opaque -1 (-2),
+// one multiply-add each; the chain normalises the difference
+template <bool THREE>
+__host__ __device__ __forceinline__ F30 norm(const int32_t *t) {
+    F30 r;
+    int32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        const int32_t s = t[i] + c;
+        r.l[i] = bal30((uint32_t)s);
+        c = THREE ? (s >> 30) + ((s >> 29) & 1) : (s + (1 << 29)) >> 30;
+    }
+    r.l[12] = t[12] + c;
+    return r;
+}
+__host__ __device__ __forceinline__ F30 sub(const F30 &a, const F30 &b) {
+    int32_t t[13];
+#pragma unroll
+    for (int i = 0; i < 13; i++) t[i] = a.l[i] - b.l[i];
+    return norm<false>(t);
+}
+__host__ __device__ __forceinline__ F30 sub2(const F30 &a, const F30 &b, const F30 &c) {
+    int32_t t[13];
+#pragma unroll
+    for (int i = 0; i < 13; i++) t[i] = a.l[i] - b.l[i] - c.l[i];
+    return norm<true>(t);
+}
+__host__ __device__ __forceinline__ F30 neg(const F30 &a) {
+    F30 r;
+#pragma unroll
+    for (int i = 0; i < 13; i++) r.l[i] = -a.l[i];
+    return r;
+}
+// a constant the compiler cannot see through (device only; emits nothing)
+__host__ __device__ __forceinline__ int32_t opaque(int32_t c) {
+#ifdef __HIP_DEVICE_COMPILE__
+    asm volatile("" : "+s"(c));
+#endif
+    return c;
+}
+// a b 2^-390 - d
+template <int CHAIN = 0>
+__host__ __device__ __forceinline__ F30 mul_sub(const F30 &a, const F30 &b, const F30 &d) {
+    const int32_t m1 = opaque(-1);
+    int32_t m[13];
+    F30 r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 25; k++) {
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) acc = mad<CHAIN>(a.l[i], b.l[k - i], acc);
+        if (k >= 13) acc = mad<CHAIN>(d.l[k - 13], m1, acc);
+        acc = pin<CHAIN>(reduce_col<CHAIN>(k, acc, m, r.l));
+    }
+    r.l[12] = (int32_t)acc - d.l[12];
+    return r;
+}
+// a^2 2^-390 - d - 2 e
+template <int CHAIN = 0>
+__host__ __device__ __forceinline__ F30 sqr_sub2(const F30 &a, const F30 &d, const F30 &e) {
+    const int32_t m1 = opaque(-1), m2 = opaque(-2);
+    int32_t m[13], a2[13];
+#pragma unroll
+    for (int i = 0; i < 13; i++) a2[i] = a.l[i] * 2;
+    F30 r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 25; k++) {
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); 2 * i < k; i++) acc = mad<CHAIN>(a.l[i], a2[k - i], acc);
+        if ((k & 1) == 0) acc = mad<CHAIN>(a.l[k / 2], a.l[k / 2], acc);
+        if (k >= 13) {
+            acc = mad<CHAIN>(d.l[k - 13], m1, acc);
+            acc = mad<CHAIN>(e.l[k - 13], m2, acc);
+        }
+        acc = pin<CHAIN>(reduce_col<CHAIN>(k, acc, m, r.l));
+    }
+    r.l[12] = (int32_t)acc - d.l[12] - 2 * e.l[12];
+    return r;
+}
 }  // namespace f30s
 
 __global__ __launch_bounds__(256) void k_mul29(uint32_t *out, int L, uint32_t seed) {
@@ -186,6 +274,28 @@ __host__ __device__ inline void mix30s(int L, f30s::F30 &a, f30s::F30 &b, f30s::
         d = f30s::mul<CHAIN>(d, ppp);
     }
 }
+// the whole mixed addition (ec30s.cuh madd30s) on (X, Y, ZZ, ZZZ) = (a, b, c, d),
+// the lane's first (a, b) added again in every step (|x2|, |y2| < 2^381, the
+// bounds of madd30s hold).  FOLD 0: the three subtractions from a fresh product
+// renormalised limb by limb, as sub() and sub2() do; FOLD 1: folded into that
+// product's reduction.  Both give the same 52 limbs (check() below).
+template <int CHAIN, int FOLD>
+__host__ __device__ inline void madd30s(int L, f30s::F30 &a, f30s::F30 &b, f30s::F30 &c, f30s::F30 &d) {
+    using namespace f30s;
+    const F30 x2 = a, y2 = b;
+#pragma unroll 1
+    for (int i = 0; i < L; i++) {
+        const F30 P = FOLD ? mul_sub<CHAIN>(x2, c, a) : sub(mul<CHAIN>(x2, c), a);
+        const F30 R = FOLD ? mul_sub<CHAIN>(y2, d, b) : sub(mul<CHAIN>(y2, d), b);
+        const F30 pp = sqr<CHAIN>(P);
+        const F30 ppp = mul<CHAIN>(P, pp), q = mul<CHAIN>(a, pp);
+        const F30 x3 = FOLD ? sqr_sub2<CHAIN>(R, ppp, q) : sub(sub2(sqr<CHAIN>(R), ppp, q), q);
+        b = mul2<CHAIN>(R, sub(q, x3), b, neg(ppp));
+        c = mul<CHAIN>(c, pp);
+        d = mul<CHAIN>(d, ppp);
+        a = x3;
+    }
+}
 
 template <int CHAIN>
 __global__ __launch_bounds__(256) void k_mul30s(uint32_t *out, int L, uint32_t seed) {
@@ -203,6 +313,16 @@ __global__ __launch_bounds__(256) void k_mix30s(uint32_t *out, int L, uint32_t s
     f30s::F30 a, b, c, d;
     seed30s(t, seed, a, b, c, d);
     mix30s<CHAIN>(L, a, b, c, d);
+    uint32_t x = 0;
+    for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
+    out[t] = x;
+}
+template <int CHAIN, int FOLD>
+__global__ __launch_bounds__(256) void k_madd30s(uint32_t *out, int L, uint32_t seed) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    f30s::F30 a, b, c, d;
+    seed30s(t, seed, a, b, c, d);
+    madd30s<CHAIN, FOLD>(L, a, b, c, d);
     uint32_t x = 0;
     for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
     out[t] = x;
@@ -287,27 +407,48 @@ static bool check(uint32_t *dout) {
     }
     printf("signed products (mul, sqr, mul2) against integer arithmetic mod q on the host: %s\n",
            bad ? "MISMATCH" : "ok");
+    {  // the folded subtractions against the renormalised ones, every limb, after each of 8 steps
+        int fb = 0;
+        for (uint32_t t = 0; t < 64; t++) {
+            f30s::F30 e, f, g, h;
+            seed30s(t, 99u, a, b, c, d);
+            e = a; f = b; g = c; h = d;
+            for (int i = 0; i < 8; i++) {
+                madd30s<0, 0>(1, a, b, c, d);
+                madd30s<0, 1>(1, e, f, g, h);
+                fb += memcmp(&a, &e, sizeof a) || memcmp(&b, &f, sizeof b) || memcmp(&c, &g, sizeof c) ||
+                      memcmp(&d, &h, sizeof d);
+            }
+        }
+        printf("mixed addition with the folded subtractions against the renormalised, limb for limb, on the host: %s\n",
+               fb ? "MISMATCH" : "ok");
+        bad += fb;
+    }
     if (dout) {  // the GPU's chains of lanes 0..255, plain and CHAIN, against the host's
-        for (int v = 0; v < 6; v++) {
+        for (int v = 0; v < 8; v++) {
             if (v == 0) hipLaunchKernelGGL(k_mul30s<0>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
             if (v == 1) hipLaunchKernelGGL(k_mul30s<1>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
             if (v == 2) hipLaunchKernelGGL(k_mul30s<2>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
             if (v == 3) hipLaunchKernelGGL(k_mix30s<0>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
             if (v == 4) hipLaunchKernelGGL(k_mix30s<1>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
             if (v == 5) hipLaunchKernelGGL(k_mix30s<2>, dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            if (v == 6) hipLaunchKernelGGL((k_madd30s<2, 0>), dim3(1), dim3(256), 0, 0, dout, 3, 5u);
+            if (v == 7) hipLaunchKernelGGL((k_madd30s<2, 1>), dim3(1), dim3(256), 0, 0, dout, 3, 5u);
             uint32_t g[256];
             if (hipMemcpy(g, dout, sizeof g, hipMemcpyDeviceToHost) != hipSuccess) return false;
             int gb = 0;
             for (uint32_t t = 0; t < 256; t++) {
                 seed30s(t, 5u, a, b, c, d);
                 if (v < 3) chain30s(3, a, b, c, d);
-                else mix30s(3, a, b, c, d);
+                else if (v < 6) mix30s(3, a, b, c, d);
+                else madd30s<0, 0>(3, a, b, c, d);
                 uint32_t x = 0;
                 for (int i = 0; i < 13; i++) x ^= (uint32_t)(a.l[i] ^ b.l[i] ^ c.l[i] ^ d.l[i]);
                 gb += x != g[t];
             }
-            printf("GPU %s, CHAIN %d, against the host's, 256 lanes: %s\n", v < 3 ? "mul chain" : "mixed-addition mix",
-                   v % 3, gb ? "MISMATCH" : "ok");
+            printf("GPU %s, CHAIN %d, against the host's, 256 lanes: %s\n",
+                   v < 3 ? "mul chain" : v < 6 ? "mixed-addition mix" : v == 6 ? "mixed addition" : "mixed addition, folded",
+                   v < 6 ? v % 3 : 2, gb ? "MISMATCH" : "ok");
             bad += gb;
         }
     }
@@ -347,7 +488,7 @@ int main(int argc, char **argv) {
     uint32_t *dout;
     if (hipMalloc(&dout, threads * 4) != hipSuccess) return 2;
     if (!check(dout)) return 1;
-    double a[3], b[3][3], m[3][3];
+    double a[3], b[3][3], m[3][3], f[2][3];
     const double mix = 3055.0 / 338.0;  // a mix iteration is 3,055 multiply-adds: counted as 3055 / 338 products
     for (int i = 0; i < 3; i++) {
         a[i] = run(k_mul29, "mul29", dout, threads, L);
@@ -357,10 +498,14 @@ int main(int argc, char **argv) {
         m[0][i] = run(k_mix30s<0>, "mix30s", dout, threads, L / 2, mix);
         m[1][i] = run(k_mix30s<1>, "mix30s/c1", dout, threads, L / 2, mix);
         m[2][i] = run(k_mix30s<2>, "mix30s/c2", dout, threads, L / 2, mix);
+        // the whole mixed addition, its products counted as the mix's: renormalised and folded subtractions
+        f[0][i] = run(k_madd30s<2, 0>, "madd30s", dout, threads, L / 2, mix);
+        f[1][i] = run(k_madd30s<2, 1>, "madd30s/f", dout, threads, L / 2, mix);
     }
     for (int i = 0; i < 3; i++) printf("ratio mul30s / mul29 = %.3f\n", b[0][i] / a[i]);
     for (int c = 1; c < 3; c++)
         for (int i = 0; i < 3; i++)
             printf("ratio CHAIN %d / plain: mul30s %.4f  mix30s %.4f\n", c, b[c][i] / b[0][i], m[c][i] / m[0][i]);
+    for (int i = 0; i < 3; i++) printf("ratio folded / renormalised subtractions: madd30s %.4f\n", f[1][i] / f[0][i]);
     return 0;
 }

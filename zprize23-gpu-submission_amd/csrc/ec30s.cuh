@@ -19,17 +19,18 @@ struct Xyzz30s {
 // (one reduction of two products < 2^766 + 2^762) < 2^381 again.  No equal /
 // opposite / infinity cases: those make ZZ = 0 mod q, detected per piece.
 // 6 mul30s + 2 sqr30s + mul2_30s = 6 338 + 2 260 + 507 = 3,055 multiply-adds
-// (the radix-2^29 form: 6 392 + 2 301 + 588 = 3,542).
+// (the radix-2^29 form: 6 392 + 2 301 + 588 = 3,542), and 12 + 12 + 24 = 48
+// more for the three subtractions from a fresh product (U2 - X, S2 - Y,
+// R^2 - PPP - 2 Q), folded into that product's reduction (mul30s_sub,
+// sqr30s_sub2): 3,103.  The results have the limbs the renormalised
+// subtractions gave, so the bounds above are what they were.
 __device__ __forceinline__ void madd30s(Xyzz30s &p, const F30s &x2, const F30s &y2) {
-    F30s u2 = mul30s(x2, p.zz);
-    F30s s2 = mul30s(y2, p.zzz);
-    F30s P = sub30s(u2, p.x);
-    F30s R = sub30s(s2, p.y);
+    F30s P = mul30s_sub(x2, p.zz, p.x);
+    F30s R = mul30s_sub(y2, p.zzz, p.y);
     F30s pp = sqr30s(P);
     F30s ppp = mul30s(P, pp);
     F30s q = mul30s(p.x, pp);
-    // two passes: a limb of R^2 - PPP - 2 Q could reach 2^31
-    F30s x3 = sub30s(sub2_30s(sqr30s(R), ppp, q), q);
+    F30s x3 = sqr30s_sub2(R, ppp, q);
     // Y3 = R (Q - X3) - Y PPP as R (Q - X3) + Y (-PPP), one reduction
     F30s y3 = mul2_30s(R, sub30s(q, x3), p.y, neg30s(ppp));
     p.zz = mul30s(p.zz, pp);

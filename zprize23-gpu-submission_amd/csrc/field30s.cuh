@@ -110,6 +110,68 @@ __device__ __forceinline__ F30s sqr30s(const F30s &a) {
     return r;
 }
 
+// A subtraction folded into the product it follows.  The reduction walks the
+// result columns 13..24 on the accumulator and takes a balanced limb out of
+// each, so a term added to column 13 + j is added to the result at weight
+// 2^(30 j): the subtrahend's limb j goes in there, times -1 (or -2), with one
+// multiply-add, and the chain normalises the difference for nothing; limb 12
+// is subtracted from what is left.  The m_k are fixed by columns 0..12, which
+// the fold does not touch, and balanced limbs 0..11 with limb 12 taking the
+// rest are unique, so the result has the 13 limbs of sub30s(mul30s(a, b), d).
+// The factor must be opaque (an SGPR the compiler cannot see through): a
+// visible -1 becomes a sign extension and a 64-bit subtract with borrow, 3
+// instructions a limb instead of one v_mad_i64_i32.
+// The subtrahend: limbs 0..11 of <= 2^29, any limb 12 that fits 32 bits with
+// the result's (here |x|, |y|, |ppp|, |q| < 2^384: limb 12 below 2^24).
+__device__ __forceinline__ int32_t opaque30s(int32_t c) {
+    asm volatile("" : "+s"(c));
+    return c;
+}
+
+// a b 2^-390 - d.  A result column holds <= 13 + 13 products of <= 2^58, a
+// carry < 2^34 and one fold term of <= 2^29: under 2^63.
+// 338 + 12 multiply-adds; |result| < 2^381 + |d|.
+__device__ __forceinline__ F30s mul30s_sub(const F30s &a, const F30s &b, const F30s &d) {
+    const int32_t m1 = opaque30s(-1);
+    int32_t m[13];
+    F30s r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 25; k++) {
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) acc = mad30s(a.l[i], b.l[k - i], acc);
+        if (k >= 13) acc = mad30s(d.l[k - 13], m1, acc);
+        acc = pin30s(reduce_col30s(k, acc, m, r));
+    }
+    r.l[12] = (int32_t)acc - d.l[12];
+    return r;
+}
+
+// a^2 2^-390 - d - 2 e.  A result column holds the <= 27 2^58 of sqr30s, a
+// carry < 2^34 and fold terms of <= 3 2^29: under 2^63.
+// 260 + 24 multiply-adds; |result| < 2^381 + |d| + 2 |e|.
+__device__ __forceinline__ F30s sqr30s_sub2(const F30s &a, const F30s &d, const F30s &e) {
+    const int32_t m1 = opaque30s(-1), m2 = opaque30s(-2);
+    int32_t m[13], a2[13];
+#pragma unroll
+    for (int i = 0; i < 13; i++) a2[i] = a.l[i] * 2;
+    F30s r;
+    int64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 25; k++) {
+#pragma unroll
+        for (int i = (k > 12 ? k - 12 : 0); 2 * i < k; i++) acc = mad30s(a.l[i], a2[k - i], acc);
+        if ((k & 1) == 0) acc = mad30s(a.l[k / 2], a.l[k / 2], acc);
+        if (k >= 13) {
+            acc = mad30s(d.l[k - 13], m1, acc);
+            acc = mad30s(e.l[k - 13], m2, acc);
+        }
+        acc = pin30s(reduce_col30s(k, acc, m, r));
+    }
+    r.l[12] = (int32_t)acc - d.l[12] - 2 * e.l[12];
+    return r;
+}
+
 // a b + c d with ONE Montgomery reduction, (a b + c d) 2^-390.  Column k
 // holds 2 n + n (+ 1) products of <= 2^58, n = min(k + 1, 25 - k): up to 39 in
 // the middle, which does not fit 63 bits.  In the columns of more than 31
