@@ -671,6 +671,44 @@ int pnp_wire_sigma(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gate
 int pnp_gather_witness(pnp_ctx *ctx, const uint32_t *const d_var[4], uint64_t n_gates,
                        const uint64_t *d_values, uint64_t n_vars, uint32_t lg_n, uint64_t *const d_w[4]);
 
+/* Extension (operator form of gen_proof's round-4 block transforms, ntt.hip).
+ * The 8n coset x_i = g w_8n^i, g = 7, is kept in "block-bitrev layout": point
+ * i = 8 j + m lives in block m at index brev(j) (brev: lg_n-bit reversal), so
+ * every block is a size-n transform of its own.  n = 2^lg_n; every array is
+ * Montgomery Fr in HBM, 4 u64 each, and every length below is in elements.
+ * m0 >= 0, nb >= 1, m0 + nb <= 8, lg_n <= 25, no NULL pointer: else PNP_E_ARG.
+ * Asynchronous on the context stream unless a mask is returned.
+ *
+ * pnp_lde_blocks: d_coeffs (n) -> d_out (nb n), d_out[b n + brev(j)] =
+ * f(g w_8n^(8 j + m0 + b)) for b < nb; form29 != 0: 32 f(..) mod r instead
+ * (the 2^261 form the quotient kernel reads).  d_out must not alias d_coeffs.
+ *
+ * pnp_to_blocks: the same permutation of values already on the coset: d_in
+ * (8 n, natural order) -> d_out (nb n), d_out[b n + brev(j)] = d_in[8 j + m0 + b].
+ *
+ * pnp_intt_blocks: d_inout (nb n) in place; block b, holding residue
+ * m = m0 + b in block-bitrev layout, becomes
+ * Y_m[u] = w_8n^(-m u) sum_j blk_m[j] w_n^(-j u), natural order, no 1 / n.
+ *
+ * pnp_t_combine_blocks: d_Y (nb n: Y_0 .. Y_(nb-1) of a polynomial of degree
+ * < nb n, nb = 6, 7 or 8) -> d_out (nb n), the coefficients in chunks:
+ * d_out[m1 n + u] = c_(u + n m1) = g^-(u + n m1) / (8 n) sum_m w_8^(-m m1) Y_m[u]
+ * (the Y_m, m >= nb, solved from the chunks m1 >= nb being zero).  *nz_out:
+ * bit m1 set iff chunk m1 < nb has a non-zero coefficient.  Synchronous.
+ *
+ * pnp_t_combine_range: the same on all 8 blocks for the coefficient indices
+ * u in [q0, q0 + len) only (one rank's share): d_Y (8 len, d_Y[m len + (u - q0)]
+ * = Y_m[u]) -> d_out (8 len), d_out[m1 len + (u - q0)] = c_(u + n m1); *nz_out
+ * as above, over this range.  q0 + len <= n.  Synchronous. */
+int pnp_lde_blocks(pnp_ctx *ctx, const uint64_t *d_coeffs, uint64_t *d_out, uint32_t lg_n, int m0, int nb,
+                   int form29);
+int pnp_to_blocks(pnp_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uint32_t lg_n, int m0, int nb);
+int pnp_intt_blocks(pnp_ctx *ctx, uint64_t *d_inout, uint32_t lg_n, int m0, int nb);
+int pnp_t_combine_blocks(pnp_ctx *ctx, const uint64_t *d_Y, int nb, uint64_t *d_out, uint32_t lg_n,
+                         unsigned *nz_out);
+int pnp_t_combine_range(pnp_ctx *ctx, const uint64_t *d_Y, uint64_t len, uint64_t q0, uint64_t *d_out,
+                        uint32_t lg_n, unsigned *nz_out);
+
 /* evaluate (function.cu:162-173): sum_i c_i x^i; x and result Montgomery,
  * host-side scalars.  Synchronous. */
 int pnp_poly_eval(pnp_ctx *ctx, const uint64_t *d_coeffs, uint64_t n,

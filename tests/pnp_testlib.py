@@ -402,6 +402,11 @@ def kzg_points(vk: np.ndarray, proof: abi.ProofC, pis, label=b"Merkle tree"):
 def inputs_vk(inp: "Inputs") -> np.ndarray:
     a = inp.arrays
     coeffs = {k: a[k + "_coeffs"] for k in VK_POLYS if k + "_coeffs" in a}
+    for t in ("table1", "table2", "table3", "table4"):
+        if a[t].any():  # (lookup_rows: the key holds the tables' row values)
+            c = a[t].copy()
+            oracle().or_ntt(vp(c), inp.lg_n, 1, 0)
+            coeffs[t] = c
     return verifier_key(coeffs, inp.n, a["srs"])
 
 

@@ -26,10 +26,21 @@ def ctx():
     c.close()
 
 
-@pytest.mark.parametrize("lg", [1, 3, 5, 9, 10, 11, 13, 16, 20])
+@pytest.mark.parametrize("lg", list(range(22)))
 def test_ntt_vs_oracle(ctx, lg):
+    """Every size from 1 to 2^21: the single-workgroup transform (lg <= 10),
+    every two-pass split from (6, 5) at 2^11 to (10, 10) at 2^20 (K = 9 with
+    lg_hlo != 0 at 2^17 .. 2^19) and the three-pass split (7, 7, 7) at 2^21."""
     rng = np.random.default_rng(100 + lg)
-    x = rand_fr_mont_arr(rng, 1 << lg)
+    if lg in (17, 18, 19, 21):
+        # (the sizes added last draw their input on the GPU: the generator is
+        # pinned below, and 2^21 values take seconds to draw on the host)
+        r = empty_dev(1 << lg)
+        ctx.random_fr(r.data_ptr(), 1 << lg, 100 + lg)
+        ctx.sync()
+        x = from_dev(r).copy()
+    else:
+        x = rand_fr_mont_arr(rng, 1 << lg)
     lib = oracle()
     for inverse, coset in [(0, 0), (1, 0), (0, 1), (1, 1)]:
         exp = x.copy()
@@ -38,6 +49,58 @@ def test_ntt_vs_oracle(ctx, lg):
         ctx.ntt(d.data_ptr(), lg, bool(inverse), bool(coset))
         got = from_dev(d)
         assert (got == exp).all(), (lg, inverse, coset)
+
+
+def _limbs(v: int) -> np.ndarray:
+    return np.array([(v >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+
+
+def _structured_inputs(lg: int):
+    """Inputs on which a wrong conditional step of the lazy residues shows
+    (ntt.hip lz_add / lz_sub / lz_mul, values in [0, 2r)): a - b = 0,
+    a + b = 2r - 2 (limbs r - 1: the largest residue), a + b = r, long runs of
+    zeros, a single live output."""
+    from pnp_testlib import fr_root, ints_to_arr
+    n = 1 << lg
+    rng = np.random.default_rng(900 + lg)
+    one, top = _limbs(fr_mont(1)), _limbs(R_MOD - 1)
+    yield "zero", np.zeros((n, 4), dtype=np.uint64)
+    yield "one", np.tile(one, (n, 1))
+    yield "r-1", np.tile(top, (n, 1))
+    for pos in (0, n - 1):
+        x = np.zeros((n, 4), dtype=np.uint64)
+        x[pos] = rand_fr_mont_arr(rng, 1)[0]
+        yield "delta%d" % pos, x
+    x = np.tile(top, (n, 1))
+    x[1::2] = _limbs(1)
+    yield "alternating", x
+    w = fr_root(lg)
+    for k in (1, n // 2, n - 1):
+        wk, p, vals = pow(w, k, R_MOD), 1, []
+        for _ in range(n):
+            vals.append(fr_mont(p))
+            p = p * wk % R_MOD
+        yield "frequency%d" % k, ints_to_arr(vals)
+    h = rand_fr_mont_arr(rng, n // 2)
+    neg = ints_to_arr([(R_MOD - from_limbs(v)) % R_MOD for v in h])
+    yield "half_negated", np.concatenate([h, neg])
+
+
+@pytest.mark.parametrize("lg", [4, 10, 11, 12, 14])
+def test_ntt_structured_inputs(ctx, lg):
+    lib = oracle()
+    for name, x in _structured_inputs(lg):
+        for inverse, coset in [(0, 0), (1, 0), (0, 1), (1, 1)]:
+            exp = x.copy()
+            lib.or_ntt(vp(exp), lg, inverse, coset)
+            d = to_dev(x)
+            ctx.ntt(d.data_ptr(), lg, bool(inverse), bool(coset))
+            assert (from_dev(d) == exp).all(), (name, lg, inverse, coset)
+        if name.startswith("frequency") and lg:
+            # (the case is what it says: one live output of the plain forward transform)
+            exp = x.copy()
+            lib.or_ntt(vp(exp), lg, 0, 0)
+            assert np.count_nonzero(exp.any(axis=1)) == 1, name
 
 
 @pytest.mark.parametrize("lg", [1, 2, 3, 5, 7])
@@ -182,7 +245,10 @@ def test_msm_edge_cases(ctx):
         assert (_commit_ck(ctx, pts, sc) == exp).all(), name
 
 
-@pytest.mark.parametrize("n", [1, 31, 32, 33, 1000, 1 << 16])
+# (1024 = 32^2 and 32768 = 32^3: the depth of the CHUNK = 32 recursions changes;
+# 4096: the batch inverse's base case; 8192 = 256 * 32: one evaluation block)
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 1000, 1 << 16,
+                               1023, 1024, 1025, 4095, 4096, 4097, 8191, 8192, 8193, 32767, 32768, 32769])
 def test_scans_vs_oracle(ctx, n):
     rng = np.random.default_rng(n + 11)
     lib = oracle()

@@ -160,6 +160,70 @@ int pnp_coset_lde8(pnp_ctx *ctx, const uint64_t *in, uint64_t *out8, uint32_t lg
     PNP_TRY(coset_lde8(ctx->ntt, in, out8, lg_n, ctx->stream));
 }
 
+// ---- operator forms of round 4's block-layout transforms (ntt.hip)
+static bool blocks_ok(uint32_t lg_n, int m0, int nb) {
+    if (m0 >= 0 && nb >= 1 && m0 + nb <= 8 && lg_n <= 25) return true;
+    set_error("coset blocks [%d, %d) of [0, 8), lg_n = %u (at most 25)", m0, m0 + nb, lg_n);
+    return false;
+}
+
+int pnp_lde_blocks(pnp_ctx *ctx, const uint64_t *d_coeffs, uint64_t *d_out, uint32_t lg_n, int m0, int nb,
+                   int form29) {
+    if (!ctx || !d_coeffs || !d_out || !blocks_ok(lg_n, m0, nb)) return PNP_E_ARG;
+    PNP_TRY(lde_blocks(ctx->ntt, d_coeffs, d_out, lg_n, m0, nb, ctx->stream, form29 != 0));
+}
+
+int pnp_intt_blocks(pnp_ctx *ctx, uint64_t *d_inout, uint32_t lg_n, int m0, int nb) {
+    if (!ctx || !d_inout || !blocks_ok(lg_n, m0, nb)) return PNP_E_ARG;
+    PNP_TRY(intt_blocks(ctx->ntt, d_inout, lg_n, m0, nb, ctx->stream));
+}
+
+int pnp_to_blocks(pnp_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uint32_t lg_n, int m0, int nb) {
+    if (!ctx || !d_in || !d_out || !blocks_ok(lg_n, m0, nb)) return PNP_E_ARG;
+    PNP_TRY(to_blocks(d_in, d_out, lg_n, m0, nb, ctx->stream));
+}
+
+// the chunk mask: the device word is zeroed first (as Proof::quotient_chunks
+// does), the combine ORs into it, and it comes back in *nz_out
+static unsigned *mask_begin(pnp_ctx *ctx) {
+    unsigned *d_nz = reinterpret_cast<unsigned *>(ctx->buf("t_nz", 1));
+    PNP_HIP(hipMemsetAsync(d_nz, 0, 4, ctx->stream));
+    return d_nz;
+}
+static void mask_end(pnp_ctx *ctx, const unsigned *d_nz, unsigned *nz_out) {
+    PNP_HIP(hipMemcpyAsync(nz_out, d_nz, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PNP_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+int pnp_t_combine_blocks(pnp_ctx *ctx, const uint64_t *d_Y, int nb, uint64_t *d_out, uint32_t lg_n,
+                         unsigned *nz_out) {
+    if (!ctx || !d_Y || !d_out || !nz_out) return PNP_E_ARG;
+    if (nb < 6 || nb > 8 || lg_n > 25) {
+        set_error("t_combine_blocks: %d blocks (6 to 8), lg_n = %u (at most 25)", nb, lg_n);
+        return PNP_E_ARG;
+    }
+    PNP_TRY({
+        unsigned *d_nz = mask_begin(ctx);
+        t_combine_blocks(ctx->ntt, d_Y, nb, d_out, lg_n, d_nz, ctx->stream);
+        mask_end(ctx, d_nz, nz_out);
+    });
+}
+
+int pnp_t_combine_range(pnp_ctx *ctx, const uint64_t *d_Y, uint64_t len, uint64_t q0, uint64_t *d_out,
+                        uint32_t lg_n, unsigned *nz_out) {
+    if (!ctx || !d_Y || !d_out || !nz_out) return PNP_E_ARG;
+    if (lg_n > 25 || q0 > (1ULL << lg_n) || len > (1ULL << lg_n) - q0) {
+        set_error("t_combine_range: [%llu, %llu + %llu) outside 2^%u (lg_n at most 25)", (unsigned long long)q0,
+                  (unsigned long long)q0, (unsigned long long)len, lg_n);
+        return PNP_E_ARG;
+    }
+    PNP_TRY({
+        unsigned *d_nz = mask_begin(ctx);
+        if (len) t_combine(ctx->ntt, d_Y, len, q0, d_out, lg_n, d_nz, ctx->stream);
+        mask_end(ctx, d_nz, nz_out);
+    });
+}
+
 int pnp_commit(pnp_ctx *ctx, const uint64_t *d_points, const uint64_t *d_scalars, uint64_t n,
                CommitmentC *out) {
     if (!ctx || !out || (n && (!d_points || !d_scalars))) return PNP_E_ARG;

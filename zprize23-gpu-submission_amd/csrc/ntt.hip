@@ -726,6 +726,9 @@ static void check_blocks(int m0, int nb) {
 void ntt_warm(NttTables &t, uint32_t lg_n, hipStream_t s) {
     for (bool inv : {false, true}) {
         ntt_twiddles(t, lg_n, inv, s);
+        // (the rows too, from the first size at which a k_ntt_pass4 runs: a
+        // proof's first transforms that read them run on the side stream)
+        if (ntt_rows_enabled() && lg_n >= 7) ntt_twiddle_rows(t, lg_n, inv, s);
         block_twist_table(t, lg_n, inv, s);
     }
     block_twist_table32(t, lg_n, s);

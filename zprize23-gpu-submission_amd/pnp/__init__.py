@@ -39,7 +39,8 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_ctx_stream", "pnp_set_exchange_ordered", "pnp_v1_context",
            "pnp_preprocess", "pnp_wire_sigma",
            "pnp_load_wire_map", "pnp_gather_witness", "pnp_prove_assignment",
-           "pnp_check_assignment", "pnp_check_witness")
+           "pnp_check_assignment", "pnp_check_witness",
+           "pnp_lde_blocks", "pnp_to_blocks", "pnp_intt_blocks", "pnp_t_combine_blocks", "pnp_t_combine_range")
 
 
 # int allgather(void *user, uint64_t bytes_per_rank) — pnp_set_msm_shard
@@ -86,7 +87,8 @@ def load(path: str = LIB_PATH):
     lib.pnp_prove.argtypes = [vp, C.POINTER(abi.CircuitC), i32, C.POINTER(abi.ProofC)]
     lib.pnp_prove_ex.argtypes = [vp, C.POINTER(abi.CircuitC), i32, u64, vp, vp, C.c_char_p,
                                  C.POINTER(abi.ProofC)]
-    for name, argtypes in list(abi.ASSIGNMENT_ARGTYPES.items()) + list(abi.CHECK_ARGTYPES.items()):
+    for name, argtypes in (list(abi.ASSIGNMENT_ARGTYPES.items()) + list(abi.CHECK_ARGTYPES.items())
+                           + list(abi.BLOCK_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.pnp_last_stage_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_char_p), i32]
     lib.pnp_kernel_timing.argtypes = [vp, i32]
@@ -354,6 +356,39 @@ class Context:
 
     def coset_lde8(self, src: int, dst: int, lg_n: int):
         check(self.lib.pnp_coset_lde8(self.h, C.c_void_p(src), C.c_void_p(dst), lg_n), "pnp_coset_lde8")
+
+    # the block-layout transforms of round 4 (include/pnp_plonk.h; n = 2^lg_n,
+    # lengths in elements)
+    def lde_blocks(self, coeffs: int, out: int, lg_n: int, m0: int, nb: int, form29: bool = False):
+        """coeffs (n) -> out (nb n): out[b n + brev(j)] = f(g w_8n^(8 j + m0 + b));
+        form29: times 32."""
+        check(self.lib.pnp_lde_blocks(self.h, C.c_void_p(coeffs or None), C.c_void_p(out or None), lg_n, m0, nb,
+                                      int(form29)), "pnp_lde_blocks")
+
+    def to_blocks(self, src: int, out: int, lg_n: int, m0: int, nb: int):
+        """src (8 n, natural) -> out (nb n): out[b n + brev(j)] = src[8 j + m0 + b]."""
+        check(self.lib.pnp_to_blocks(self.h, C.c_void_p(src or None), C.c_void_p(out or None), lg_n, m0, nb),
+              "pnp_to_blocks")
+
+    def intt_blocks(self, addr: int, lg_n: int, m0: int, nb: int):
+        """addr (nb n) in place: the unscaled inverse transform and twist of each block."""
+        check(self.lib.pnp_intt_blocks(self.h, C.c_void_p(addr or None), lg_n, m0, nb), "pnp_intt_blocks")
+
+    def t_combine_blocks(self, Y: int, nb: int, out: int, lg_n: int) -> int:
+        """Y (nb n), nb in 6..8 -> out (nb n) coefficient chunks; returns the
+        mask of the non-zero chunks."""
+        nz = C.c_uint()
+        check(self.lib.pnp_t_combine_blocks(self.h, C.c_void_p(Y or None), nb, C.c_void_p(out or None), lg_n,
+                                            C.byref(nz)), "pnp_t_combine_blocks")
+        return nz.value
+
+    def t_combine_range(self, Y: int, length: int, q0: int, out: int, lg_n: int) -> int:
+        """Y (8 length) -> out (8 length): the coefficients u in [q0, q0 +
+        length) of every chunk; returns the mask of the non-zero chunks."""
+        nz = C.c_uint()
+        check(self.lib.pnp_t_combine_range(self.h, C.c_void_p(Y or None), length, q0, C.c_void_p(out or None), lg_n,
+                                           C.byref(nz)), "pnp_t_combine_range")
+        return nz.value
 
     def commit(self, points: int, scalars: int, n: int) -> abi.CommitmentC:
         out = abi.CommitmentC()

@@ -156,7 +156,22 @@ CHECK_ARGTYPES = {
                           C.POINTER(CheckReport)],
 }
 
-assert C.sizeof(CheckReport) == (2 + len(CHECK_KINDS)) * 8 + 16
+# The block-layout transforms of round 4 in operator form (HBM addresses).
+#   pnp_lde_blocks(ctx, d_coeffs, d_out, lg_n, m0, nb, form29)
+#   pnp_to_blocks(ctx, d_in, d_out, lg_n, m0, nb)
+#   pnp_intt_blocks(ctx, d_inout, lg_n, m0, nb)
+#   pnp_t_combine_blocks(ctx, d_Y, nb, d_out, lg_n, nz_out)
+#   pnp_t_combine_range(ctx, d_Y, len, q0, d_out, lg_n, nz_out)
+BLOCK_ARGTYPES = {
+    "pnp_lde_blocks": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int],
+    "pnp_to_blocks": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int],
+    "pnp_intt_blocks": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int],
+    "pnp_t_combine_blocks": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint)],
+    "pnp_t_combine_range": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                            C.POINTER(C.c_uint)],
+}
+
+assert C.sizeof(CheckReport) ==(2 + len(CHECK_KINDS)) * 8 + 16
 assert C.sizeof(VerifierKey) == 8 + 96 + 23 * 96
 assert C.sizeof(CircuitDesc) == 3 * 8 + (4 + 15 + 4) * 8
 assert C.sizeof(ProofC) == 2656
