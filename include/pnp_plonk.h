@@ -501,6 +501,79 @@ int pnp_check_witness(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs,
                       uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
                       pnp_check_report *report /* may be NULL */);
 
+/* The witness from the circuit's inputs: the library computes the assignment
+ * itself, over the resident wire map and the key's selector rows, instead of
+ * the composer filling it gate by gate on the CPU (the reference's witness
+ * generation: 9-10 s at HEIGHT 15, run twice, circuit.rs:311).  A general
+ * arithmetic-gate solver: almost every variable of a composer-built circuit is
+ * the one unknown of one arithmetic row whose other wires are known.
+ *
+ * The plan (pnp_load_solve_inputs), once per circuit and per choice of input
+ * variables.  Slots of a row and their selectors: a (q_l, q_hl, q_m),
+ * b (q_r, q_hr, q_m), c (q_o), d (q_4, q_h4).  A slot of row i is RELEVANT when
+ * q_arith[i] != 0 and any of its selectors is non-zero at row i, and SOLVABLE
+ * when its linear selector (q_l, q_r, q_o, q_4) is non-zero and its other
+ * selectors are zero.  K_0 = the input variables.  In round t a row is READY
+ * when exactly one relevant slot holds a variable u outside K_(t-1) (u in two
+ * relevant slots: not ready) and that slot is solvable; among the rows ready
+ * for the same u the lowest defines it, the others stay plain constraints;
+ * K_t = K_(t-1) + the round's targets; the first round without a ready row
+ * ends it.  Rows of the custom gates and the lookup, and rows with
+ * q_arith = 0, never define anything: variables only they touch must be
+ * inputs.  The defining equation is
+ *   u = -(S + PI_i / q_arith_i) / coef,
+ * S the arithmetic sum of the row (q_m ab + q_l a + ... + q_c) with u's slot
+ * and every slot that is not relevant taken as 0, PI_i the public input at
+ * that row (0 without one), coef the linear selector of u's slot.  -1 / coef
+ * is folded into the stored coefficients, so a solve inverts nothing and
+ * cannot fail.  The plan is stored in level (round) order, within a level by
+ * variable id, and is the same on every run; it is built on the device from
+ * forward transforms of the resident selector coefficients into scratch that
+ * is released before the call returns.
+ *   input_ids: n_inputs distinct variable ids (host, or HBM with device_ptrs).
+ *   info (may be NULL): n_inputs, n_solved, n_levels (rounds), max_width (the
+ *   widest level), n_undetermined / first_undetermined (~0: none), plan_bytes.
+ *   PNP_E_NOKEY  no prover key, or no wire map resident
+ *   PNP_E_ARG    an id >= n_vars, an id listed twice, or a variable that is
+ *                neither an input nor defined by any round (info is filled);
+ *                pnp_last_error names the lowest such id.  A sharded context
+ *                (as pnp_preprocess).  After PNP_E_ARG no plan is resident.
+ * The plan is replaced by the next pnp_load_solve_inputs and dropped, with
+ * the solution, by whatever drops or replaces the wire map.
+ *
+ * pnp_solve_assignment: inputs[k] = the Montgomery value of input_ids[k], host
+ * memory (one staged upload) or HBM (16-byte aligned).  Public inputs as
+ * pnp_prove_ex; they matter on defining rows only — a variable whose defining
+ * row carries a public input takes its value from it (the Merkle circuit's
+ * root variable is defined by the root row, PI = -root, from round 2 on:
+ * INTEGRATION.md 4 has the flow).  Writes all n_vars values into a buffer the
+ * context owns, rewritten by the next solve and dropped with the plan; a level
+ * wider than a workgroup is one launch, a run of narrower levels one launch of
+ * one workgroup.  Nothing says whether the inputs satisfy the rows that define
+ * nothing: pnp_check_assignment does.  Stage times solve_inputs, solve_levels
+ * (ms) and the count inputs_h2d_bytes (pnp_last_stage_times); the level
+ * kernels are timed as "solve_levels" (pnp_kernel_timing).
+ *   PNP_E_NOKEY  no plan resident          PNP_E_ARG  n_inputs differs from the plan's
+ * pnp_assignment_ptr: the solution in HBM (n_vars Montgomery Fr), for
+ * pnp_prove_assignment / pnp_check_assignment with device_ptrs = 1.
+ * pnp_assignment_values: k values of it to host memory, out[4 j ..] = the value
+ * of ids[j] (ids NULL: the first k variables); how a host without HIP reads
+ * the Merkle root.  Both: PNP_E_NOKEY before a solve, PNP_E_ARG for an id or k
+ * beyond n_vars.
+ * pnp_hbm_usage out[0] counts the plan (plan_bytes) and the solution (32 n_vars).
+ * All four are synchronous and single GPU. */
+typedef struct {
+    uint64_t n_inputs, n_solved, n_levels, max_width;
+    uint64_t n_undetermined, first_undetermined;   /* first: ~0 when none */
+    uint64_t plan_bytes;
+} pnp_solve_info;
+int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, int device_ptrs,
+                          pnp_solve_info *info /* may be NULL */);
+int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs,
+                         uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon);
+int pnp_assignment_ptr(pnp_ctx *ctx, uint64_t **d_values, uint64_t *n_vars);
+int pnp_assignment_values(pnp_ctx *ctx, const uint32_t *ids, uint64_t k, uint64_t *out);
+
 /* Per-stage wall-clock (ms) of the last pnp_prove, for the bench/profiles.
  * Writes up to `cap` doubles and their names; returns the stage count. */
 int pnp_last_stage_times(pnp_ctx *ctx, double *ms, const char **names, int cap);
@@ -772,6 +845,7 @@ static_assert(sizeof(CommitKeyC) == 16, "CommitKeyC layout (lib.rs:225-229)");
 static_assert(sizeof(pnp_verifier_key) == 8 + 96 + PNP_VK_POLYS * 96, "pnp_verifier_key layout (or_verifier_key)");
 static_assert(sizeof(pnp_circuit_desc) == 3 * 8 + (4 + 15 + 4) * 8, "pnp_circuit_desc layout");
 static_assert(sizeof(pnp_check_report) == (2 + PNP_CHECK_KINDS) * 8 + 4 * 4, "pnp_check_report layout");
+static_assert(sizeof(pnp_solve_info) == 7 * 8, "pnp_solve_info layout");
 #else
 _Static_assert(sizeof(ProofC) == 2656, "ProofC layout (lib.rs:120-142)");
 _Static_assert(sizeof(ProverKeyC) == 44 * 8, "ProverKeyC layout (lib.rs:157-223)");

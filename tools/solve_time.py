@@ -1,0 +1,286 @@
+#!/usr/bin/env python3
+"""Time the witness solver at the bench's size (one GPU process; run it once,
+under a timeout of its own):
+
+    timeout -k 10 900 python tools/solve_time.py [--height 15] [--out profiles/solve_time.json]
+
+The circuit is the reference's Poseidon Merkle tree at HEIGHT (15: 3,161,924
+rows on D = 2^22, 3,194,709 variables) as tests/merkle_circuit.py lays it out.
+Building that composer in Python would take minutes, so the wire map, the
+selector rows and the input list are tiled with numpy from the per-hash
+template (193 rows, 193 fresh variables) taken from merkle_circuit(3); before
+anything runs on the GPU the tiling is asserted to reproduce merkle_circuit(6)
+exactly (wire map, every selector row, n_vars, the input ids).  The inputs are
+the 8 blinding values, the leaves and the per-hash domain tags; the root (for
+the public input, which defines the root variable) comes from the native
+Poseidon tree on the CPU.
+
+Measured: pnp_preprocess, the plan build (pnp_load_solve_inputs, three times),
+the solve alone, and after the warm-up proofs two paths interleaved, --reps of
+each: solve + prove from the resident solution, against prove from the same
+assignment uploaded from host memory.  The solution must pass
+pnp_check_assignment, hold the CPU's root, and every proof must be the same
+bytes."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "zprize23-gpu-submission_amd"), os.path.join(REPO, "tests")]
+
+HASH_ROWS = 193   # rows, and fresh variables, per hash
+HEAD_ROWS = 4     # zero_var's gate and the three blinding rows
+ZERO, LEFT, RIGHT, NODE = -1, -2, -3, -4
+SELECTORS = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_hl", "q_hr", "q_h4", "q_arith")
+
+
+def shape(height):
+    leaves = 1 << (height - 1)
+    hashes = leaves - 1
+    return leaves, hashes, HASH_ROWS * hashes + HEAD_ROWS + 1, 9 + leaves + hashes + HASH_ROWS * hashes
+
+
+def hash_order(height):
+    """Node index of every hash in row order (constraints.rs:39-99: the bottom
+    non-leaf level first, then upwards; within a level ascending)."""
+    starts, idx = [], 0
+    for _ in range(height - 1):
+        starts.append(idx)
+        idx = 2 * idx + 1
+    return np.concatenate([np.arange(s, 2 * s + 1, dtype=np.int64) for s in reversed(starts)])
+
+
+def template(height=3):
+    """(codes (4, 193), head ids (4, 4), {selector: (head, hash, last) canonical ints}) from merkle_circuit(height):
+    a wire of the first hash is a fresh variable of the hash (its offset), zero_var, the hash's left or right input,
+    or the node it is asserted equal to."""
+    import merkle_circuit as mc
+    cp = mc.merkle_circuit(height, seed=1)[0]
+    leaves, hashes, ng, n_vars = shape(height)
+    assert (len(cp.rows), len(cp.vals)) == (ng, n_vars)
+    base = 9 + leaves + hashes
+    node = 9 + leaves + int(hash_order(height)[0])
+    named = {0: ZERO, 9: LEFT, 10: RIGHT, node: NODE}
+    codes = np.zeros((4, HASH_ROWS), dtype=np.int64)
+    for k in range(HASH_ROWS):
+        for j, v in enumerate(cp.rows[HEAD_ROWS + k][1]):
+            codes[j, k] = v - base if base <= v < base + HASH_ROWS else named[v]
+    head = np.array([cp.rows[i][1] for i in range(HEAD_ROWS)], dtype=np.int64).T
+    assert cp.rows[-1][1] == (9 + leaves, 0, 0, 0)
+    sel = {}
+    for name in SELECTORS:
+        col = [r[0].get(name, 0) for r in cp.rows]
+        # every hash has the template's selectors
+        assert all(col[HEAD_ROWS + HASH_ROWS * h:HEAD_ROWS + HASH_ROWS * (h + 1)] == col[HEAD_ROWS:HEAD_ROWS + HASH_ROWS]
+                   for h in range(hashes))
+        sel[name] = (col[:HEAD_ROWS], col[HEAD_ROWS:HEAD_ROWS + HASH_ROWS], col[-1:])
+    return codes, head, sel
+
+
+def tile(height, tpl):
+    """(var (4, n_gates) u32, {selector: canonical ints by part}, input ids, n_vars, root variable) at `height`."""
+    codes, head, sel = tpl
+    leaves, hashes, ng, n_vars = shape(height)
+    node_i = hash_order(height)
+    base = 9 + leaves + hashes + HASH_ROWS * np.arange(hashes, dtype=np.int64)
+    bottom = node_i >= leaves // 2 - 1
+    left = np.where(bottom, 9 + 2 * node_i + 1 - (leaves - 1), 9 + leaves + 2 * node_i + 1)
+    named = {ZERO: np.zeros(hashes, dtype=np.int64), LEFT: left, RIGHT: left + 1, NODE: 9 + leaves + node_i}
+    var = np.zeros((4, ng), dtype=np.uint32)
+    var[:, :HEAD_ROWS] = head
+    for j in range(4):
+        block = base[:, None] + codes[j][None, :]
+        for code, ids in named.items():
+            block = np.where(codes[j][None, :] == code, ids[:, None], block)
+        var[j, HEAD_ROWS:ng - 1] = block.reshape(-1)
+    var[:, ng - 1] = (9 + leaves, 0, 0, 0)
+    ids = np.concatenate([np.arange(1, 9 + leaves), var[0, HEAD_ROWS:ng - 1:HASH_ROWS].astype(np.int64)])
+    return var, sel, ids.astype(np.uint32), n_vars, 9 + leaves
+
+
+def mont_rows(ints):
+    from pnp_testlib import fr_mont, ints_to_arr
+    return ints_to_arr([fr_mont(v) for v in ints])
+
+
+def selector_column(parts, hashes):
+    head, one, last = (mont_rows(p) for p in parts)
+    return np.ascontiguousarray(np.concatenate([head, np.tile(one, (hashes, 1)), last]))
+
+
+def assert_tiling_reproduces(height, tpl):
+    import merkle_circuit as mc
+    from solve_ref import merkle_inputs
+    from test_preprocess_ref import wire_map
+    cp = mc.merkle_circuit(height, seed=2)[0]
+    var, sel, ids, n_vars, root_var = tile(height, tpl)
+    assert n_vars == len(cp.vals) and np.array_equal(var, wire_map(cp))
+    hashes = shape(height)[1]
+    for name in SELECTORS:
+        assert np.array_equal(selector_column(sel[name], hashes), mont_rows([r[0].get(name, 0) for r in cp.rows])), name
+    assert list(ids) == merkle_inputs(cp) and cp.rows[-1][1][0] == root_var
+    assert not any(r[0].get(k) for r in cp.rows for k in r[0] if k not in SELECTORS)
+
+
+def median(xs):
+    return sorted(xs)[len(xs) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--height", type=int, default=15)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=15)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "solve_time.json"))
+    args = ap.parse_args()
+    reps = max(args.reps, 5)
+
+    t0 = time.perf_counter()
+    tpl = template()
+    assert_tiling_reproduces(6, tpl)
+    from pnp_testlib import R_MOD, fr_mont, ints_to_arr
+    from merkle_circuit import merkle_tree
+    from poseidon import PoseidonConstants
+    height = args.height
+    leaves, hashes, ng, n_vars = shape(height)
+    D = 1 << max(4, (ng - 1).bit_length())
+    var, sel, ids, n_vars, root_var = tile(height, tpl)
+    cols = {name: selector_column(parts, hashes) for name, parts in sel.items() if any(any(p) for p in parts)}
+    rng = np.random.default_rng(args.seed)
+    rnd = lambda: int.from_bytes(rng.bytes(32), "little") % R_MOD
+    pc = PoseidonConstants()
+    blind, leaf_vals = [rnd() for _ in range(8)], [rnd() for _ in range(leaves)]
+    t1 = time.perf_counter()
+    root = merkle_tree(pc, leaf_vals)[0]
+    cpu_tree_s = time.perf_counter() - t1
+    inputs = ints_to_arr([fr_mont(v) for v in blind + leaf_vals + [pc.domain_tag] * hashes])
+    assert len(inputs) == len(ids)
+    pis = [(ng - 1, -root % R_MOD)]
+    build_s = time.perf_counter() - t0
+
+    import torch
+    import pnp
+    from pnp import abi
+    if not torch.cuda.is_available():
+        raise SystemExit("solve_time: no GPU (a measurement needs one; nothing is written)")
+    desc = abi.CircuitDesc(n_gates=ng, n_vars=n_vars, lookup_len=0)
+    for j in range(4):
+        desc.var[j] = var[j].ctypes.data_as(abi.U32P)
+    for k, name in enumerate(abi.DESC_SELECTORS):
+        if name in cols:
+            desc.sel[k] = cols[name].ctypes.data_as(abi.U64P)
+    ctx = pnp.Context(0)
+    srs = torch.zeros((D, 12), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    ctx.srs(srs.data_ptr(), D, [5, 0, 0, 0])
+    ctx.sync()
+    ck = abi.CommitKeyC(powers_of_g=abi.ptr(srs.data_ptr()), powers_of_gamma_g=abi.ptr(srs.data_ptr()))
+    ctx.load_commit_key(ck, D, device_ptrs=True)
+    t0 = time.perf_counter()
+    ctx.preprocess(desc, device_ptrs=False)
+    preprocess_s = time.perf_counter() - t0
+
+    plan_s, infos = [], []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        rc, info = ctx.load_solve_inputs(ids.ctypes.data, len(ids), False)
+        plan_s.append(time.perf_counter() - t0)
+        if rc != 0:
+            raise SystemExit(f"solve_time: no plan: {ctx.last_error()}")
+        infos.append(bytes(info))
+    if len(set(infos)) != 1 or info.n_solved + info.n_inputs != n_vars:
+        raise SystemExit("solve_time: the plan differs between builds, or does not cover every variable")
+
+    def solve():
+        t0 = time.perf_counter()
+        ctx.solve_assignment(inputs.ctypes.data, len(ids), False, pis)
+        return time.perf_counter() - t0, dict(ctx.stage_times())
+
+    solve()
+    addr, n = ctx.assignment_ptr()
+    ok, rep = ctx.check_assignment(addr, n_vars, True, pis)
+    if not ok:
+        raise SystemExit(f"solve_time: the solution fails the check: {ctx.last_error()}")
+    (limbs,) = ctx.assignment_values(ids=[root_var])
+    if sum(int(w) << (64 * k) for k, w in enumerate(limbs)) != fr_mont(root):
+        raise SystemExit("solve_time: the solution's root is not the CPU tree's")
+    host_values = np.zeros((n_vars, 4), dtype=np.uint64)
+    if ctx.lib.pnp_assignment_values(ctx.h, None, n_vars, host_values.ctypes.data) != 0:
+        raise SystemExit("solve_time: " + ctx.last_error())
+
+    def solve_and_prove():
+        t0 = time.perf_counter()
+        ctx.solve_assignment(inputs.ctypes.data, len(ids), False, pis)
+        st = dict(ctx.stage_times())
+        addr, n = ctx.assignment_ptr()
+        p = ctx.prove_assignment(addr, n, True, pis)
+        return abi.proof_to_bytes(p), time.perf_counter() - t0, st
+
+    def upload_and_prove():
+        t0 = time.perf_counter()
+        p = ctx.prove_assignment(host_values.ctypes.data, n_vars, False, pis)
+        return abi.proof_to_bytes(p), time.perf_counter() - t0, dict(ctx.stage_times())
+
+    # warm-up: the first proof goes without the context's tables, which are then
+    # built in the background (pnp_sync waits for them); one more of each path
+    ref, _, _ = upload_and_prove()
+    ctx.sync()
+    proofs = [solve_and_prove()[0], upload_and_prove()[0]]
+    ctx.sync()
+    runs = {"solve_and_prove": [], "upload_and_prove": []}
+    solve_stages = []
+    for _ in range(reps):
+        proof, wall, st = solve_and_prove()
+        proofs.append(proof)
+        runs["solve_and_prove"].append(wall)
+        solve_stages.append(st)
+        proof, wall, _ = upload_and_prove()
+        proofs.append(proof)
+        runs["upload_and_prove"].append(wall)
+    solve_alone = [solve()[0] for _ in range(reps)]
+    all_equal = all(p == ref for p in proofs)
+    # the level kernels' own time: one more solve with the event timers on
+    ctx.kernel_timing(True)
+    solve()
+    levels_ms, _ = ctx.kernel_stats("solve_levels")
+    levels_bytes = ctx.kernel_bytes("solve_levels")
+    ctx.kernel_timing(False)
+    hbm = ctx.hbm_usage()["live"]
+    ctx.close()
+
+    med = {k: median(v) for k, v in runs.items()}
+    out = {
+        "height": height, "lg": D.bit_length() - 1, "n_gates": ng, "n_vars": n_vars, "n_inputs": int(info.n_inputs),
+        "n_solved": int(info.n_solved), "n_levels": int(info.n_levels), "max_width": int(info.max_width),
+        "plan_bytes": int(info.plan_bytes), "inputs_bytes": int(inputs.nbytes), "assignment_bytes": 32 * n_vars,
+        "tiling_reproduces_merkle_circuit_6": True, "solution_passes_check_assignment": True,
+        "solution_root_equals_cpu_tree": True, "plan_same_on_every_build": True,
+        "plan_build_s_runs": [round(x, 4) for x in plan_s], "plan_build_s": round(median(plan_s), 4),
+        "solve_s_runs": [round(x, 5) for x in solve_alone], "solve_s": round(median(solve_alone), 5),
+        "solve_stage_ms_median": {k: round(median([st[k] for st in solve_stages]), 4)
+                                  for k in ("solve_inputs", "solve_levels")},
+        "levels_kernels_ms": round(levels_ms, 4), "levels_kernels_bytes": int(levels_bytes),
+        "levels_kernels_gb_s": round(levels_bytes / (levels_ms * 1e-3) / 1e9, 1) if levels_ms > 0 else None,
+        "reps_each": reps, "interleaved": True, "all_proofs_equal": bool(all_equal), "proofs_compared": len(proofs) + 1,
+        "median_s": {k: round(v, 5) for k, v in med.items()},
+        "wall_s_runs": {k: [round(x, 5) for x in v] for k, v in runs.items()},
+        "solve_and_prove_over_upload_and_prove": round(med["solve_and_prove"] / med["upload_and_prove"], 4),
+        "hbm_live_bytes_at_end": int(hbm),
+        "host_side_s": {"build_instance": round(build_s, 2), "cpu_poseidon_tree": round(cpu_tree_s, 2),
+                        "preprocess": round(preprocess_s, 3)},
+    }
+    if not all_equal:
+        raise SystemExit("solve_time: the proofs differ")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -3,7 +3,9 @@
 // context.cpp, the proof prover.cpp, the prover-key loads prover_key.cpp; the
 // v1 gen_proof, which wraps them in the reference's contract, is v1.cpp.  The
 // satisfiability check (pnp_check_assignment, pnp_check_witness) is whole
-// here, over the kernels of check.hip.
+// here, over the kernels of check.hip, and so is the witness solver
+// (pnp_load_solve_inputs, pnp_solve_assignment) over those of solve.hip.
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <stdlib.h>
@@ -780,6 +782,251 @@ int pnp_last_stage_times(pnp_ctx *ctx, double *ms, const char **names, int cap) 
         k++;
     }
     return k;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the witness solver
+namespace {
+
+void solve_refuse_sharded(pnp_ctx *ctx, const char *what) {
+    if (ctx->msm.world > 1) {
+        set_error("%s: the context is sharded over %d ranks (a multi-rank solve is not supported)", what,
+                  ctx->msm.world);
+        throw pnp::Error(PNP_E_ARG);
+    }
+}
+
+const pnp::ResidentKey::SolvePlan &solved_plan(pnp_ctx *ctx) {
+    const pnp::ResidentKey::SolvePlan &sp = ctx->key.solve;
+    if (!sp.loaded || !sp.solution.p) {
+        set_error("no solved assignment resident (pnp_load_solve_inputs and pnp_solve_assignment first)");
+        throw pnp::Error(PNP_E_NOKEY);
+    }
+    return sp;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, int device_ptrs,
+                          pnp_solve_info *info) {
+    if (!ctx || (n_inputs && !input_ids) || n_inputs > 0xffffffffULL) return PNP_E_ARG;
+    PNP_TRY({
+        using namespace pnp;
+        if (info) {
+            memset(info, 0, sizeof *info);
+            info->first_undetermined = ~0ULL;
+        }
+        ResidentKey &key = ctx->key;
+        if (!key.loaded || !key.wm_loaded) {
+            set_error(key.loaded ? "no wire map resident (pnp_preprocess or pnp_load_wire_map first)"
+                                 : "prover key not loaded");
+            throw Error(PNP_E_NOKEY);
+        }
+        solve_refuse_sharded(ctx, "load solve inputs");
+        tables_wait(ctx);  // (the NTT tables are shared with a background build)
+        PNP_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        key.solve.drop();
+        const uint64_t D = key.n, ng = key.wm_gates, n_vars = key.wm_vars;
+        const uint32_t lg = log2_exact(D);
+
+        // the input ids, and every variable's level: 0 for an input
+        DevBuf ids(4 * std::max<uint64_t>(n_inputs, 1)), level(4 * n_vars), def(4 * n_vars), small;
+        if (n_inputs)
+            PNP_HIP(hipMemcpyAsync(ids.p, input_ids, 4 * n_inputs,
+                                   device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        uint32_t err[2];
+        solve_mark_inputs(ids.u32(), n_inputs, n_vars, level.u32(), err, small, s);
+        if (err[0] != 0xffffffffu) {
+            set_error("load solve inputs: input id %u is not a variable (n_vars = %llu)", err[0],
+                      (unsigned long long)n_vars);
+            throw Error(PNP_E_ARG);
+        }
+        if (err[1] != 0xffffffffu) {
+            set_error("load solve inputs: input id %u is listed twice", err[1]);
+            throw Error(PNP_E_ARG);
+        }
+
+        // the selector rows: forward transforms of the resident coefficients (as Check::check_columns)
+        DevBuf rows[kKeyRows];
+        const uint64_t *const *coeffs = reinterpret_cast<const uint64_t *const *>(&key.dev);
+        auto row_values = [&](KeyPoly r) -> const uint64_t * {
+            if (!key.has(r)) return nullptr;
+            rows[r].alloc(32 * D);
+            ntt_run(ctx->ntt, rows[r].u64(), lg, false, false, s, coeffs[kKeyTable[r].coeffs]);
+            return rows[r].u64();
+        };
+        SolveSel sel{};
+        sel.q_m = row_values(kQm), sel.q_l = row_values(kQl), sel.q_r = row_values(kQr), sel.q_o = row_values(kQo);
+        sel.q_4 = row_values(kQ4), sel.q_c = row_values(kQc), sel.q_hl = row_values(kQhl);
+        sel.q_hr = row_values(kQhr), sel.q_h4 = row_values(kQh4), sel.q_arith = row_values(kQarith);
+
+        const uint32_t *var = key.wm_var.u32();
+        const uint32_t *dvar[4] = {var, var + ng, var + 2 * ng, var + 3 * ng};
+        SolveBuild b;
+        solve_rounds(dvar, ng, n_vars, sel, level.u32(), def.u32(), b, s);
+        pnp_solve_info out;
+        memset(&out, 0, sizeof out);
+        out.n_inputs = n_inputs;
+        out.n_levels = b.widths.size();
+        for (uint32_t w : b.widths) {
+            out.n_solved += w;
+            out.max_width = std::max<uint64_t>(out.max_width, w);
+        }
+        out.n_undetermined = b.n_undetermined;
+        out.first_undetermined = b.n_undetermined ? b.first_undetermined : ~0ULL;
+        if (b.n_undetermined) {
+            if (info) *info = out;
+            set_error("load solve inputs: variable %u is neither an input nor defined by an arithmetic row whose other "
+                      "wires are known (%llu such variables)",
+                      b.first_undetermined, (unsigned long long)b.n_undetermined);
+            throw Error(PNP_E_ARG);
+        }
+
+        ResidentKey::SolvePlan &sp = key.solve;
+        sp.buf.alloc(SolveView::bytes(out.n_solved, out.n_levels, n_inputs, sel.q_m != nullptr));
+        sp.view.lay(sp.buf.p, out.n_solved, out.n_levels, sel.q_m != nullptr);
+        solve_emit(dvar, n_vars, sel, level.u32(), def.u32(), b, sp.view, s);
+        if (n_inputs) PNP_HIP(hipMemcpyAsync(sp.view.ids, ids.p, 4 * n_inputs, hipMemcpyDeviceToDevice, s));
+        PNP_HIP(hipStreamSynchronize(s));
+        // the launches: a level wider than a workgroup alone, narrower ones in runs
+        uint64_t p = 0;
+        for (uint32_t l = 0; l < b.widths.size(); l++) {
+            const bool wide = b.widths[l] > 256;
+            if (!wide && !sp.runs.empty() && !sp.runs.back().wide) {
+                sp.runs.back().l1 = l + 1;
+                sp.runs.back().p1 = p + b.widths[l];
+            } else {
+                sp.runs.push_back({l, l + 1, p, p + b.widths[l], wide});
+            }
+            p += b.widths[l];
+        }
+        sp.n_inputs = n_inputs;
+        sp.n_solved = out.n_solved;
+        sp.n_levels = out.n_levels;
+        sp.loaded = true;
+        out.plan_bytes = sp.buf.bytes;
+        if (info) *info = out;
+    });
+}
+
+int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs, uint64_t n_pi,
+                         const uint64_t *pi_pos, const uint64_t *pi_canon) {
+    if (!ctx || (n_inputs && !inputs) || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
+    if (device_ptrs && ((uintptr_t)inputs & 15)) {
+        set_error("solve assignment: HBM inputs must be 16-byte aligned");
+        return PNP_E_ARG;
+    }
+    PNP_TRY({
+        using namespace pnp;
+        ResidentKey::SolvePlan &sp = ctx->key.solve;
+        if (!sp.loaded) {
+            set_error("no solve plan resident (pnp_load_solve_inputs first)");
+            throw Error(PNP_E_NOKEY);
+        }
+        if (n_inputs != sp.n_inputs) {
+            set_error("solve assignment: %llu inputs, the plan was built for %llu", (unsigned long long)n_inputs,
+                      (unsigned long long)sp.n_inputs);
+            throw Error(PNP_E_ARG);
+        }
+        solve_refuse_sharded(ctx, "solve assignment");
+        const ProveOpts opt{n_pi, pi_pos, pi_canon, nullptr};
+        std::vector<uint64_t> pos;
+        std::vector<Fr> val;
+        public_input_map(opt, ctx->key.n, pos, val);
+        tables_wait(ctx);
+        PNP_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        ctx->stages.clear();
+        auto t0 = std::chrono::steady_clock::now();
+        auto mark = [&](const char *name) {
+            PNP_HIP(hipStreamSynchronize(s));
+            const auto t1 = std::chrono::steady_clock::now();
+            ctx->stages.emplace_back(name, std::chrono::duration<double, std::milli>(t1 - t0).count());
+            t0 = t1;
+        };
+
+        const uint64_t n_vars = ctx->key.wm_vars;
+        if (!sp.solution.p) sp.solution.alloc(32 * n_vars);
+        uint64_t *vals = sp.solution.u64();
+        // (a slot that is not relevant may name a variable a later level writes: it reads zero)
+        PNP_HIP(hipMemsetAsync(vals, 0, 32 * n_vars, s));
+        DevBuf up, pis;
+        const uint64_t *in = inputs;
+        if (n_inputs && !device_ptrs) {
+            up.alloc(32 * n_inputs);
+            h2d_batch(ctx, {{up.p, inputs, 32 * n_inputs}});
+            in = up.u64();
+        }
+        k_solve_scatter(sp.view.ids, in, n_inputs, vals, s);
+        const uint64_t *d_pos = nullptr, *d_val = nullptr;
+        if (!pos.empty()) {  // ascending rows, then their Montgomery values 16-byte aligned (as the check)
+            const size_t val_off = (pos.size() + 1) & ~size_t(1);
+            std::vector<uint64_t> packed(val_off + 4 * pos.size());
+            for (size_t k = 0; k < pos.size(); k++) {
+                packed[k] = pos[k];
+                to_u64_limbs(val[k], &packed[val_off + 4 * k]);
+            }
+            pis.alloc(8 * packed.size());
+            PNP_HIP(hipMemcpyAsync(pis.p, packed.data(), 8 * packed.size(), hipMemcpyHostToDevice, s));
+            PNP_HIP(hipStreamSynchronize(s));
+            d_pos = pis.u64();
+            d_val = pis.u64() + val_off;
+        }
+        mark("solve_inputs");
+
+        hipEvent_t e0 = nullptr;
+        ctx->ktimer.begin("solve_levels", s, e0);
+        for (const auto &r : sp.runs)
+            k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, r.wide, vals, d_pos, d_val, (uint32_t)pos.size(), s);
+        // an entry reads its coefficients and ids, four values, and writes one
+        const double per_entry = 32.0 * (kSolveCoefs - (sp.view.coef[kSolveQm] ? 1 : 2)) + 4 * 6 + 32 * 5;
+        ctx->ktimer.end("solve_levels", s, e0, per_entry * (double)sp.n_solved);
+        mark("solve_levels");
+        ctx->ktimer.collect();
+        ctx->stages.emplace_back("inputs_h2d_bytes", device_ptrs ? 0.0 : 32.0 * (double)n_inputs);
+    });
+}
+
+int pnp_assignment_ptr(pnp_ctx *ctx, uint64_t **d_values, uint64_t *n_vars) {
+    if (!ctx || !d_values) return PNP_E_ARG;
+    PNP_TRY({
+        const pnp::ResidentKey::SolvePlan &sp = solved_plan(ctx);
+        *d_values = sp.solution.u64();
+        if (n_vars) *n_vars = ctx->key.wm_vars;
+    });
+}
+
+int pnp_assignment_values(pnp_ctx *ctx, const uint32_t *ids, uint64_t k, uint64_t *out) {
+    if (!ctx || (k && !out)) return PNP_E_ARG;
+    PNP_TRY({
+        const pnp::ResidentKey::SolvePlan &sp = solved_plan(ctx);
+        const uint64_t n_vars = ctx->key.wm_vars;
+        if (k > n_vars && !ids) {
+            set_error("assignment values: %llu values of %llu variables", (unsigned long long)k,
+                      (unsigned long long)n_vars);
+            throw pnp::Error(PNP_E_ARG);
+        }
+        for (uint64_t j = 0; ids && j < k; j++)
+            if (ids[j] >= n_vars) {
+                set_error("assignment values: id %u is not a variable (n_vars = %llu)", ids[j],
+                          (unsigned long long)n_vars);
+                throw pnp::Error(PNP_E_ARG);
+            }
+        PNP_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        if (!ids) {
+            if (k) PNP_HIP(hipMemcpyAsync(out, sp.solution.p, 32 * k, hipMemcpyDeviceToHost, s));
+        } else {
+            for (uint64_t j = 0; j < k; j++)  // (a handful of values: the root)
+                PNP_HIP(hipMemcpyAsync(out + 4 * j, sp.solution.u64() + 4 * (uint64_t)ids[j], 32,
+                                       hipMemcpyDeviceToHost, s));
+        }
+        PNP_HIP(hipStreamSynchronize(s));
+    });
 }
 
 }  // extern "C"

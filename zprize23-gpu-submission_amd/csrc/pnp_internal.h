@@ -306,6 +306,10 @@ uint64_t wire_sigma_scratch_bytes(uint64_t n_gates);
 uint64_t wire_sigma(NttTables &ntt, const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, uint32_t lg,
                     uint32_t *d_next, uint64_t *const d_sigma[4], DevBuf &scratch, hipStream_t s,
                     WireSigmaStats *stats = nullptr);
+// the permutation's stable radix sort for any m u32 keys below 2^bits (bits >=
+// 1): order[p] = the position the p-th smallest key came from, equal keys in
+// position order.  The result lies in `scratch` (grown to fit); asynchronous
+const uint32_t *sort_positions_u32(const uint32_t *d_keys, uint64_t m, int bits, DevBuf &scratch, hipStream_t s);
 // dst[i] = src[i], i < n; then src[0] (first) or zero up to D; dst == src pads in place
 void k_pad_col(uint64_t *dst, const uint64_t *src, uint64_t n, uint64_t D, bool first, hipStream_t s);
 // ---- the witness from a variable assignment (assignment.hip) ----
@@ -350,6 +354,56 @@ void k_check_lookup(const uint64_t *const w[4], const uint64_t *s_rows, uint64_t
 // maps) is skipped
 void k_check_copy(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const uint64_t *const w[4],
                   uint32_t lg, uint32_t *first, CheckRecord *rec, hipStream_t s);
+
+// ---- the witness from the circuit's inputs (solve.hip) ----
+// the selector rows the plan is built from: D rows each, HBM; q_m nullptr = zero
+struct SolveSel {
+    const uint64_t *q_m, *q_l, *q_r, *q_o, *q_4, *q_c, *q_hl, *q_hr, *q_h4, *q_arith;
+};
+// A plan in HBM, level order: entry p defines variable tgt[p] from row row[p] as
+//   q_l' a + q_r' b + q_o' c + q_4' d + q_hl' a^5 + q_hr' b^5 + q_h4' d^5 + q_m' a b + q_c' + pik PI_row,
+// a .. d the values of var[0..3][p]; every q' is the row's selector times
+// -1 / coef, zero for the target's own slot and for slots that are not
+// relevant; pik = -1 / (coef q_arith).  Level l is entries lvl_off[l] ..
+// lvl_off[l + 1].  n entries; the arrays start 16-byte aligned.
+enum { kSolveQl, kSolveQr, kSolveQo, kSolveQ4, kSolveQhl, kSolveQhr, kSolveQh4, kSolveQc, kSolvePik, kSolveQm,
+       kSolveCoefs };
+struct SolveView {
+    uint64_t *coef[kSolveCoefs];  // coef[kSolveQm] nullptr: the key has no q_m
+    uint32_t *tgt, *row, *var[4], *lvl_off, *ids;
+    static uint64_t padded(uint64_t n) { return (n + 3) & ~3ULL; }
+    static uint64_t bytes(uint64_t n, uint64_t n_levels, uint64_t n_inputs, bool qm) {
+        return padded(n) * (32 * (kSolveCoefs - (qm ? 0 : 1)) + 4 * 6) + 4 * padded(n_levels + 1) + 4 * padded(n_inputs);
+    }
+    void lay(void *base, uint64_t n, uint64_t n_levels, bool qm);
+};
+// What the plan build leaves on the host: per level its width (the rounds of
+// include/pnp_plonk.h's plan rules), and what stayed undetermined.
+struct SolveBuild {
+    std::vector<uint32_t> widths;
+    uint64_t n_undetermined = 0;
+    uint32_t first_undetermined = 0xffffffffu;
+};
+// level[u] = 0 for the n_inputs listed variables (UNSET before); returns the
+// lowest id >= n_vars in err[0], the lowest id listed twice in err[1] (~0: none)
+void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars, uint32_t *d_level, uint32_t err[2],
+                       DevBuf &scratch, hipStream_t s);
+// the rounds: d_level[u] = the round that defines u (1-based), d_def[u] = 4 row
+// + slot of its defining row; d_level / d_def: n_vars u32, d_level as
+// solve_mark_inputs left it.  Synchronous (one read-back a round)
+void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
+                  uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s);
+// the plan's entries in (level, variable id) order from d_level / d_def; the
+// inversions by k_batch_inverse.  `v` laid over a buffer of SolveView::bytes
+void solve_emit(const uint32_t *const d_var[4], uint64_t n_vars, const SolveSel &sel, const uint32_t *d_level,
+                const uint32_t *d_def, const SolveBuild &b, const SolveView &v, hipStream_t s);
+// vals[ids[k]] = in[k]
+void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inputs, uint64_t *d_vals, hipStream_t s);
+// levels [l0, l1) of the plan: each level one launch when `wide`, else all of
+// them in one launch of one workgroup (every level at most 256 entries).
+// pi_pos / pi_val as CheckRows
+void k_solve_levels(const SolveView &v, uint32_t l0, uint32_t l1, uint64_t p0, uint64_t p1, bool wide, uint64_t *d_vals,
+                    const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s);
 
 void k_synth_merkle(int height, const uint64_t *pc_mont_host, const uint64_t *leaves, const uint64_t *blind,
                     uint64_t *nodes, uint64_t *const w[4], uint64_t *const sel[9], uint64_t *const sigma[4],

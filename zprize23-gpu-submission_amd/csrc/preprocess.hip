@@ -289,10 +289,56 @@ void k_pad_col(uint64_t *dst, const uint64_t *src, uint64_t n, uint64_t D, bool 
     PNP_HIP(hipGetLastError());
 }
 
-uint64_t wire_sigma_scratch_bytes(uint64_t n_gates) {
-    const uint64_t m = 4 * n_gates, ntiles = (m + PNP_SIGMA_TILE - 1) / PNP_SIGMA_TILE;
+// the sort's buffers in one allocation of sort_bytes(m): two key and two value
+// arrays of m u32 (a pass reads one pair and writes the other), the (digit,
+// tile) histogram, the scan's segment sums, and 256 spare bytes behind them
+struct SortLayout {
+    uint64_t m, hist_n;
+    uint32_t ntiles, nseg;
+    uint32_t *key[2], *val[2], *hist, *sums;
+    SortLayout(uint32_t *buf, uint64_t m_) : m(m_) {
+        ntiles = (uint32_t)((m + PNP_SIGMA_TILE - 1) / PNP_SIGMA_TILE);
+        hist_n = (uint64_t)SORT_BINS * ntiles;
+        nseg = (uint32_t)((hist_n + SCAN_SPAN - 1) / SCAN_SPAN);
+        key[0] = buf, key[1] = buf + m, val[0] = buf + 2 * m, val[1] = buf + 3 * m;
+        hist = buf + 4 * m, sums = hist + hist_n;
+    }
+};
+static uint64_t sort_bytes(uint64_t m) {
+    const uint64_t ntiles = (m + PNP_SIGMA_TILE - 1) / PNP_SIGMA_TILE;
     const uint64_t hist = SORT_BINS * ntiles, nseg = (hist + SCAN_SPAN - 1) / SCAN_SPAN;
     return 4 * m * 4 + hist * 4 + nseg * 4 + 256;
+}
+// `passes` 8-bit passes over the keys in key[0] (values: the positions);
+// returns the pair holding the result
+static int sort_passes(const SortLayout &l, int passes, hipStream_t s) {
+    int cur = 0;
+    for (int pass = 0; pass < passes; pass++, cur ^= 1) {
+        const int shift = 8 * pass;
+        hipLaunchKernelGGL(k_sort_hist, dim3(l.ntiles), dim3(SORT_THREADS), 0, s, l.key[cur], l.m, shift, l.ntiles,
+                           l.hist);
+        hipLaunchKernelGGL(k_scan_sums, dim3(l.nseg), dim3(256), 0, s, l.hist, l.hist_n, l.sums);
+        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, l.sums, l.nseg);
+        hipLaunchKernelGGL(k_scan_apply, dim3(l.nseg), dim3(256), 0, s, l.hist, l.hist_n, l.sums);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(l.ntiles), dim3(SORT_THREADS), 0, s, l.key[cur],
+                           pass ? l.val[cur] : nullptr, l.m, shift, l.ntiles, l.hist, l.key[cur ^ 1], l.val[cur ^ 1]);
+        PNP_HIP(hipGetLastError());
+    }
+    return cur;
+}
+
+uint64_t wire_sigma_scratch_bytes(uint64_t n_gates) { return sort_bytes(4 * n_gates); }
+
+// The same stable sort for any m u32 keys below 2^bits (solve.hip: variables
+// by level): order[p] = the position the p-th smallest key came from, equal
+// keys in position order.  The keys are copied, the result lies in `scratch`
+// (grown to fit).  bits >= 1.  Asynchronous on s.
+const uint32_t *sort_positions_u32(const uint32_t *d_keys, uint64_t m, int bits, DevBuf &scratch, hipStream_t s) {
+    scratch.reserve(sort_bytes(m));
+    const SortLayout lay(static_cast<uint32_t *>(scratch.p), m);
+    PNP_HIP(hipMemcpyAsync(lay.key[0], d_keys, 4 * m, hipMemcpyDeviceToDevice, s));
+    const int passes = (std::max(bits, 1) + 7) / 8;
+    return lay.val[sort_passes(lay, passes, s)];
 }
 
 // next (4 D u32, must not be null) and the sigma columns (each may be null)
@@ -303,13 +349,10 @@ uint64_t wire_sigma(NttTables &ntt, const uint32_t *const d_var[4], uint64_t n_g
                     uint32_t *d_next, uint64_t *const d_sigma[4], DevBuf &scratch, hipStream_t s,
                     WireSigmaStats *stats) {
     const uint64_t m = 4 * n_gates, D = 1ULL << lg;
-    const uint32_t ntiles = (uint32_t)((m + PNP_SIGMA_TILE - 1) / PNP_SIGMA_TILE);
-    const uint64_t hist_n = (uint64_t)SORT_BINS * ntiles;
-    const uint32_t nseg = (uint32_t)((hist_n + SCAN_SPAN - 1) / SCAN_SPAN);
     scratch.reserve(wire_sigma_scratch_bytes(n_gates));
-    uint32_t *buf = static_cast<uint32_t *>(scratch.p);
-    uint32_t *key[2] = {buf, buf + m}, *val[2] = {buf + 2 * m, buf + 3 * m};
-    uint32_t *hist = buf + 4 * m, *sums = hist + hist_n, *bad = sums + nseg;
+    const SortLayout lay(static_cast<uint32_t *>(scratch.p), m);
+    uint32_t *const *key = lay.key, *const *val = lay.val;
+    uint32_t *bad = lay.sums + lay.nseg;
     PNP_HIP(hipMemsetAsync(bad, 0xff, 4, s));
     hipLaunchKernelGGL(k_wire_keys, dim3(nblk(n_gates)), dim3(256), 0, s, d_var[0], d_var[1], d_var[2], d_var[3],
                        n_gates, n_vars, key[0], bad);
@@ -319,17 +362,7 @@ uint64_t wire_sigma(NttTables &ntt, const uint32_t *const d_var[4], uint64_t n_g
     const uint64_t top = std::min<uint64_t>(n_vars, 1ULL << 32) - 1;
     while (bits < 32 && (top >> bits)) bits++;
     const int passes = (bits + 7) / 8;
-    int cur = 0;
-    for (int pass = 0; pass < passes; pass++, cur ^= 1) {
-        const int shift = 8 * pass;
-        hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(SORT_THREADS), 0, s, key[cur], m, shift, ntiles, hist);
-        hipLaunchKernelGGL(k_scan_sums, dim3(nseg), dim3(256), 0, s, hist, hist_n, sums);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, sums, nseg);
-        hipLaunchKernelGGL(k_scan_apply, dim3(nseg), dim3(256), 0, s, hist, hist_n, sums);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(SORT_THREADS), 0, s, key[cur],
-                           pass ? val[cur] : nullptr, m, shift, ntiles, hist, key[cur ^ 1], val[cur ^ 1]);
-        PNP_HIP(hipGetLastError());
-    }
+    const int cur = sort_passes(lay, passes, s);
     hipLaunchKernelGGL(k_link, dim3(nblk(m)), dim3(256), 0, s, key[cur], passes ? val[cur] : nullptr, m, lg, d_next);
     if (n_gates < D)
         hipLaunchKernelGGL(k_next_identity, dim3(nblk(4 * (D - n_gates))), dim3(256), 0, s, d_next, n_gates, lg);

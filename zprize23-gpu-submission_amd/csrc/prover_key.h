@@ -190,7 +190,35 @@ struct ResidentKey {
         wm_gates = wm_vars = 0;
         wm_var.release();
         wm_qlk.release();
+        solve.drop();  // a plan is a schedule of this map's rows
     }
+
+    // ---- the witness solver's plan and solution (pnp_load_solve_inputs,
+    // pnp_solve_assignment; solve.hip) ----
+    // Built over the resident wire map for one choice of input variables;
+    // replaced by the next pnp_load_solve_inputs, dropped with the map
+    struct SolvePlan {
+        bool loaded = false;
+        uint64_t n_inputs = 0, n_solved = 0, n_levels = 0;
+        DevBuf buf;      // the entries, the level offsets, the input ids (SolveView)
+        SolveView view{};
+        // the launches of a solve: one wide level (more than a workgroup), or a
+        // run of consecutive levels that each fit one
+        struct Run {
+            uint32_t l0, l1;
+            uint64_t p0, p1;
+            bool wide;
+        };
+        std::vector<Run> runs;
+        DevBuf solution;  // n_vars Fr of the last solve; empty before it
+        void drop() {
+            loaded = false;
+            n_inputs = n_solved = n_levels = 0;
+            buf.release();
+            runs.clear();
+            solution.release();
+        }
+    } solve;
 };
 
 }  // namespace pnp

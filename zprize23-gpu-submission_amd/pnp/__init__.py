@@ -40,6 +40,7 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_preprocess", "pnp_wire_sigma",
            "pnp_load_wire_map", "pnp_gather_witness", "pnp_prove_assignment",
            "pnp_check_assignment", "pnp_check_witness",
+           "pnp_load_solve_inputs", "pnp_solve_assignment", "pnp_assignment_ptr", "pnp_assignment_values",
            "pnp_lde_blocks", "pnp_to_blocks", "pnp_intt_blocks", "pnp_t_combine_blocks", "pnp_t_combine_range")
 
 
@@ -88,7 +89,7 @@ def load(path: str = LIB_PATH):
     lib.pnp_prove_ex.argtypes = [vp, C.POINTER(abi.CircuitC), i32, u64, vp, vp, C.c_char_p,
                                  C.POINTER(abi.ProofC)]
     for name, argtypes in (list(abi.ASSIGNMENT_ARGTYPES.items()) + list(abi.CHECK_ARGTYPES.items())
-                           + list(abi.BLOCK_ARGTYPES.items())):
+                           + list(abi.SOLVE_ARGTYPES.items()) + list(abi.BLOCK_ARGTYPES.items())):
         getattr(lib, name).argtypes = argtypes
     lib.pnp_last_stage_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_char_p), i32]
     lib.pnp_kernel_timing.argtypes = [vp, i32]
@@ -280,6 +281,44 @@ class Context:
         rc = self.lib.pnp_check_witness(self.h, C.byref(cs), int(device_ptrs), k, C.cast(pos, C.c_void_p),
                                         C.cast(vals, C.c_void_p), C.byref(rep))
         return self._checked(rc, rep, "pnp_check_witness")
+
+    # ---- the witness from the circuit's inputs
+    def load_solve_inputs(self, ids: int, n_inputs: int, device_ptrs: bool = False):
+        """pnp_load_solve_inputs: ids = address (host, or HBM with device_ptrs)
+        of n_inputs u32 variable ids.  Returns (rc, abi.SolveInfo); raises on
+        every error but PNP_E_ARG, whose info says what stayed undetermined
+        (last_error() names the id)."""
+        info = abi.SolveInfo()
+        rc = self.lib.pnp_load_solve_inputs(self.h, C.c_void_p(ids or None), n_inputs, int(device_ptrs),
+                                            C.byref(info))
+        if rc != -1:
+            check(rc, "pnp_load_solve_inputs")
+        return rc, info
+
+    def solve_assignment(self, inputs: int, n_inputs: int, device_ptrs: bool, pis=()):
+        """pnp_solve_assignment: inputs = address of n_inputs Montgomery Fr, in
+        the order of the ids the plan was loaded with; pis as prove_ex."""
+        k, pos, vals = self._pi_args(list(pis))
+        check(self.lib.pnp_solve_assignment(self.h, C.c_void_p(inputs or None), n_inputs, int(device_ptrs), k,
+                                            C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p)),
+              "pnp_solve_assignment")
+
+    def assignment_ptr(self):
+        """pnp_assignment_ptr: (HBM address, n_vars) of the resident solution."""
+        p, n = C.c_void_p(), C.c_uint64()
+        check(self.lib.pnp_assignment_ptr(self.h, C.byref(p), C.byref(n)), "pnp_assignment_ptr")
+        return p.value, n.value
+
+    def assignment_values(self, ids=None, k: int = None):
+        """pnp_assignment_values: the Montgomery values (lists of 4 u64 limbs)
+        of the variables `ids`, or of the first k variables."""
+        if ids is not None:
+            k = len(ids)
+            arr = (C.c_uint32 * max(k, 1))(*ids)
+        out = (C.c_uint64 * max(4 * k, 1))()
+        check(self.lib.pnp_assignment_values(self.h, C.cast(arr, C.c_void_p) if ids is not None else None, k,
+                                             C.cast(out, C.c_void_p)), "pnp_assignment_values")
+        return [list(out[4 * j:4 * j + 4]) for j in range(k)]
 
     def last_error(self) -> str:
         msg = self.lib.pnp_last_error()

@@ -156,6 +156,26 @@ CHECK_ARGTYPES = {
                           C.POINTER(CheckReport)],
 }
 
+class SolveInfo(C.Structure):
+    """pnp_solve_info: what a solve plan covers.  n_levels rounds, the widest
+    max_width entries; first_undetermined = 2^64 - 1 when every variable is
+    an input or solved; plan_bytes = the HBM the resident plan holds."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_inputs", "n_solved", "n_levels", "max_width", "n_undetermined",
+                                          "first_undetermined", "plan_bytes")]
+
+
+# The witness solver.
+#   pnp_load_solve_inputs(ctx, input_ids, n_inputs, device_ptrs, info)
+#   pnp_solve_assignment(ctx, inputs, n_inputs, device_ptrs, n_pi, pi_pos, pi_canon)
+#   pnp_assignment_ptr(ctx, &d_values, &n_vars)
+#   pnp_assignment_values(ctx, ids, k, out)
+SOLVE_ARGTYPES = {
+    "pnp_load_solve_inputs": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(SolveInfo)],
+    "pnp_solve_assignment": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p],
+    "pnp_assignment_ptr": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)],
+    "pnp_assignment_values": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p],
+}
+
 # The block-layout transforms of round 4 in operator form (HBM addresses).
 #   pnp_lde_blocks(ctx, d_coeffs, d_out, lg_n, m0, nb, form29)
 #   pnp_to_blocks(ctx, d_in, d_out, lg_n, m0, nb)
@@ -172,6 +192,7 @@ BLOCK_ARGTYPES = {
 }
 
 assert C.sizeof(CheckReport) ==(2 + len(CHECK_KINDS)) * 8 + 16
+assert C.sizeof(SolveInfo) == 7 * 8
 assert C.sizeof(VerifierKey) == 8 + 96 + 23 * 96
 assert C.sizeof(CircuitDesc) == 3 * 8 + (4 + 15 + 4) * 8
 assert C.sizeof(ProofC) == 2656
