@@ -538,7 +538,8 @@ int pnp_check_witness(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs,
  *                neither an input nor defined by any round (info is filled);
  *                pnp_last_error names the lowest such id.  A sharded context
  *                (as pnp_preprocess).  After PNP_E_ARG no plan is resident.
- * The plan is replaced by the next pnp_load_solve_inputs and dropped, with
+ * The plan is replaced by the next plan build (this call or
+ * pnp_load_solve_plan, below: this call is that one without output rows) and dropped, with
  * the solution, by whatever drops or replaces the wire map.
  *
  * pnp_solve_assignment: inputs[k] = the Montgomery value of input_ids[k], host
@@ -573,6 +574,59 @@ int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs
                          uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon);
 int pnp_assignment_ptr(pnp_ctx *ctx, uint64_t **d_values, uint64_t *n_vars);
 int pnp_assignment_values(pnp_ctx *ctx, const uint32_t *ids, uint64_t k, uint64_t *out);
+
+/* Public inputs that are outputs of the computation (a tree root, a hash, a
+ * commitment opened to the verifier): the library derives them from the solve
+ * instead of being told them.  An OUTPUT ROW is a row whose public input is
+ * derived.  Two additions to the plan rules above, nothing else changes:
+ *   - an output row is never READY: it defines nothing in any round (its mask
+ *     byte is zero from the start of the plan build, no sweep looks at it);
+ *   - after the last level, for every output row i,  PI_i = -q_arith_i S_i,
+ *     S_i the full arithmetic sum of row i over the solved values, every slot
+ *     as it stands (a slot that is not relevant only meets zero coefficients).
+ * The Merkle circuit's root row, root 1 - 0 + PI = 0, as an output row: the
+ * root variable is then defined by the root's assert_equal row from the last
+ * hash's output (one more round), and PI = -root comes out of the solve.
+ *
+ * pnp_load_solve_plan is pnp_load_solve_inputs with output rows; that call is
+ * this one with n_outputs = 0 (same info, same plan_bytes, same plan).
+ * output_rows: n_outputs distinct row indices, as pi_pos, host memory or HBM
+ * with device_ptrs (which speaks for both lists).  They are checked on the
+ * device, the lowest offending row named, the same on every run:
+ *   PNP_E_ARG  "output row R is not a gate" (R >= n_gates), "output row R is
+ *              listed twice", "output row R has q_arith = 0" (its identity
+ *              forces PI = 0: nothing can be derived there), in that order;
+ *              no plan is resident afterwards.  A variable that only an output
+ *              row could have defined is undetermined, reported as above.
+ * The plan gains one entry per output row, in listed order after the levels
+ * and counted in plan_bytes: the row, its four variable ids, the row's nine
+ * selectors q_l q_r q_o q_4 q_hl q_hr q_h4 q_c q_m (q_m only when the key has
+ * it) each already multiplied by -q_arith, and 32 bytes for the derived value.
+ *
+ * pnp_solve_assignment on a plan with outputs: a pi_pos that names an output
+ * row is PNP_E_ARG ("row R is an output of the plan"); other public inputs act
+ * on defining rows as before.  After the last level one more launch, a lane an
+ * output row, writes PI_i in canonical form, and the call copies them to the
+ * host.  The stage list gains solve_outputs (ms) after solve_levels, only when
+ * the plan has outputs.
+ * pnp_solved_public_inputs: the (row, canonical value) pairs of the last solve
+ * in listed order; *n = their count, min(cap, *n) pairs are written (pos[k],
+ * canon[4 k ..]).  A derived zero is reported as zero (the proving call drops
+ * it like any zero public input).  PNP_E_NOKEY before a solve, PNP_E_ARG for
+ * n NULL.
+ * pnp_prove_solved / pnp_check_solved: pnp_prove_assignment /
+ * pnp_check_assignment over the resident solution (pnp_assignment_ptr) with
+ * the caller's public inputs followed by the derived ones: the same proof
+ * bytes, the same report, the same errors.  A caller's pi_pos on an output row
+ * is PNP_E_ARG; PNP_E_NOKEY before a solve. */
+int pnp_load_solve_plan(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs,
+                        const uint64_t *output_rows, uint64_t n_outputs, int device_ptrs,
+                        pnp_solve_info *info /* may be NULL */);
+int pnp_solved_public_inputs(pnp_ctx *ctx, uint64_t *pos, uint64_t *canon, uint64_t cap, uint64_t *n);
+int pnp_prove_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
+                     const char *label, ProofC *out);
+int pnp_check_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
+                     pnp_check_report *report /* may be NULL */);
 
 /* Per-stage wall-clock (ms) of the last pnp_prove, for the bench/profiles.
  * Writes up to `cap` doubles and their names; returns the stage count. */

@@ -20,7 +20,19 @@ the solve alone, and after the warm-up proofs two paths interleaved, --reps of
 each: solve + prove from the resident solution, against prove from the same
 assignment uploaded from host memory.  The solution must pass
 pnp_check_assignment, hold the CPU's root, and every proof must be the same
-bytes."""
+bytes.
+
+    timeout -k 10 900 python tools/solve_time.py --outputs [--out profiles/solve_outputs_time.json]
+
+The root row as an output of the plan (pnp_load_solve_plan): the solve is given
+the leaves and no public input, PI = -root comes out of it, pnp_prove_solved
+proves, and nothing computes the root on the CPU before the proofs.  Beside it,
+in the same process, the present path: the plan without outputs, the solve and
+the proof given the public input (here the derived one).  After two warm-up
+visits --reps visits of each path, interleaved; a visit is the plan build, a
+solve, and a solve + prove, each timed.  Afterwards the native tree is
+computed once and the derived root compared with it; every proof of both paths
+must be the same bytes."""
 import argparse
 import json
 import os
@@ -130,59 +142,199 @@ def median(xs):
     return sorted(xs)[len(xs) // 2]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--height", type=int, default=15)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--seed", type=int, default=15)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "solve_time.json"))
-    args = ap.parse_args()
-    reps = max(args.reps, 5)
-
+def setup(args, with_root):
+    """The instance at args.height and a context with its key and wire map
+    resident.  with_root: the root from the native Poseidon tree on the CPU
+    (r.root, r.cpu_tree_s); without it nothing here knows the root."""
+    from types import SimpleNamespace
+    r = SimpleNamespace()
     t0 = time.perf_counter()
     tpl = template()
     assert_tiling_reproduces(6, tpl)
     from pnp_testlib import R_MOD, fr_mont, ints_to_arr
     from merkle_circuit import merkle_tree
     from poseidon import PoseidonConstants
-    height = args.height
-    leaves, hashes, ng, n_vars = shape(height)
-    D = 1 << max(4, (ng - 1).bit_length())
-    var, sel, ids, n_vars, root_var = tile(height, tpl)
-    cols = {name: selector_column(parts, hashes) for name, parts in sel.items() if any(any(p) for p in parts)}
+    r.height = args.height
+    r.leaves, r.hashes, r.ng, r.n_vars = shape(r.height)
+    r.D = 1 << max(4, (r.ng - 1).bit_length())
+    r.var, sel, r.ids, r.n_vars, r.root_var = tile(r.height, tpl)
+    r.cols = {name: selector_column(parts, r.hashes) for name, parts in sel.items() if any(any(p) for p in parts)}
     rng = np.random.default_rng(args.seed)
     rnd = lambda: int.from_bytes(rng.bytes(32), "little") % R_MOD
     pc = PoseidonConstants()
-    blind, leaf_vals = [rnd() for _ in range(8)], [rnd() for _ in range(leaves)]
-    t1 = time.perf_counter()
-    root = merkle_tree(pc, leaf_vals)[0]
-    cpu_tree_s = time.perf_counter() - t1
-    inputs = ints_to_arr([fr_mont(v) for v in blind + leaf_vals + [pc.domain_tag] * hashes])
-    assert len(inputs) == len(ids)
-    pis = [(ng - 1, -root % R_MOD)]
-    build_s = time.perf_counter() - t0
+    blind, r.leaf_vals = [rnd() for _ in range(8)], [rnd() for _ in range(r.leaves)]
+    r.cpu_root = lambda: merkle_tree(pc, r.leaf_vals)[0]
+    r.root = r.cpu_tree_s = None
+    if with_root:
+        t1 = time.perf_counter()
+        r.root = r.cpu_root()
+        r.cpu_tree_s = time.perf_counter() - t1
+    r.inputs = ints_to_arr([fr_mont(v) for v in blind + r.leaf_vals + [pc.domain_tag] * r.hashes])
+    assert len(r.inputs) == len(r.ids)
+    r.build_s = time.perf_counter() - t0
 
     import torch
     import pnp
     from pnp import abi
     if not torch.cuda.is_available():
         raise SystemExit("solve_time: no GPU (a measurement needs one; nothing is written)")
-    desc = abi.CircuitDesc(n_gates=ng, n_vars=n_vars, lookup_len=0)
+    desc = abi.CircuitDesc(n_gates=r.ng, n_vars=r.n_vars, lookup_len=0)
     for j in range(4):
-        desc.var[j] = var[j].ctypes.data_as(abi.U32P)
+        desc.var[j] = r.var[j].ctypes.data_as(abi.U32P)
     for k, name in enumerate(abi.DESC_SELECTORS):
-        if name in cols:
-            desc.sel[k] = cols[name].ctypes.data_as(abi.U64P)
-    ctx = pnp.Context(0)
-    srs = torch.zeros((D, 12), dtype=torch.int64, device="cuda")
+        if name in r.cols:
+            desc.sel[k] = r.cols[name].ctypes.data_as(abi.U64P)
+    r.ctx = ctx = pnp.Context(0)
+    r.srs = torch.zeros((r.D, 12), dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
-    ctx.srs(srs.data_ptr(), D, [5, 0, 0, 0])
+    ctx.srs(r.srs.data_ptr(), r.D, [5, 0, 0, 0])
     ctx.sync()
-    ck = abi.CommitKeyC(powers_of_g=abi.ptr(srs.data_ptr()), powers_of_gamma_g=abi.ptr(srs.data_ptr()))
-    ctx.load_commit_key(ck, D, device_ptrs=True)
+    ck = abi.CommitKeyC(powers_of_g=abi.ptr(r.srs.data_ptr()), powers_of_gamma_g=abi.ptr(r.srs.data_ptr()))
+    ctx.load_commit_key(ck, r.D, device_ptrs=True)
     t0 = time.perf_counter()
     ctx.preprocess(desc, device_ptrs=False)
-    preprocess_s = time.perf_counter() - t0
+    r.preprocess_s = time.perf_counter() - t0
+    return r
+
+
+def spread(xs):
+    return max(xs) - min(xs)
+
+
+def main_outputs(args, reps):
+    """The root row as an output of the plan: nothing computes the root on the
+    CPU before the proofs; the present path (PI given, here the derived one)
+    runs beside it, plan build, solve and solve + prove interleaved."""
+    from pnp import abi
+    from pnp_testlib import R_MOD
+    r = setup(args, with_root=False)
+    ctx, ids, inputs, n_vars = r.ctx, r.ids, r.inputs, r.n_vars
+    root_row = np.array([r.ng - 1], dtype=np.uint64)
+
+    def timed(f, *a):
+        t0 = time.perf_counter()
+        out = f(*a)
+        return time.perf_counter() - t0, out
+
+    def plan(outputs):
+        if outputs:
+            rc, info = ctx.load_solve_plan(ids.ctypes.data, len(ids), root_row.ctypes.data, 1, False)
+        else:
+            rc, info = ctx.load_solve_inputs(ids.ctypes.data, len(ids), False)
+        if rc != 0 or info.n_solved + info.n_inputs != n_vars:
+            raise SystemExit(f"solve_time: no plan: {ctx.last_error()}")
+        return info
+
+    def solve(pis):
+        ctx.solve_assignment(inputs.ctypes.data, len(ids), False, pis)
+        return dict(ctx.stage_times())
+
+    def solve_and_prove(outputs, pis):
+        ctx.solve_assignment(inputs.ctypes.data, len(ids), False, [] if outputs else pis)
+        if outputs:
+            return abi.proof_to_bytes(ctx.prove_solved([]))
+        addr, n = ctx.assignment_ptr()
+        return abi.proof_to_bytes(ctx.prove_assignment(addr, n, True, pis))
+
+    def visit(outputs, pis, keep):
+        """One path once: its plan, a solve, a solve + prove."""
+        t_plan, info = timed(plan, outputs)
+        t_solve, st = timed(solve, [] if outputs else pis)
+        t_both, proof = timed(solve_and_prove, outputs, pis)
+        if keep is not None:
+            keep["plan_build"].append(t_plan)
+            keep["solve"].append(t_solve)
+            keep["solve_and_prove"].append(t_both)
+            keep["stages"].append(st)
+        return info, proof
+
+    # the derived root is what the present path is given: nothing else knows it yet
+    plan(True)
+    solve([])
+    derived = ctx.solved_public_inputs()
+    ok, rep = ctx.check_solved([])
+    if not ok or [p for p, _ in derived] != [r.ng - 1]:
+        raise SystemExit(f"solve_time: the solution fails the check: {ctx.last_error()}")
+    # warm-up: the first proof goes without the context's tables, which are then
+    # built in the background (pnp_sync waits for them); one more visit of each path
+    info_out, ref = visit(True, derived, None)
+    ctx.sync()
+    info_in, proof = visit(False, derived, None)
+    proofs = [proof, visit(True, derived, None)[1]]
+    ctx.sync()
+    runs = {"outputs": {"plan_build": [], "solve": [], "solve_and_prove": [], "stages": []},
+            "given": {"plan_build": [], "solve": [], "solve_and_prove": [], "stages": []}}
+    infos = {"outputs": [bytes(info_out)], "given": [bytes(info_in)]}
+    for _ in range(reps):
+        for name, outputs in (("outputs", True), ("given", False)):
+            info, proof = visit(outputs, derived, runs[name])
+            infos[name].append(bytes(info))
+            proofs.append(proof)
+            if outputs and ctx.solved_public_inputs() != derived:
+                raise SystemExit("solve_time: the derived public input differs between solves")
+    hbm = ctx.hbm_usage()["live"]
+    ctx.close()
+    all_equal = all(p == ref for p in proofs)
+    same_plans = all(len(set(v)) == 1 for v in infos.values())
+    # only now the native tree, once, as a check
+    t0 = time.perf_counter()
+    root = r.cpu_root()
+    cpu_tree_s = time.perf_counter() - t0
+    root_ok = derived == [(r.ng - 1, -root % R_MOD)]
+
+    out = {"height": r.height, "lg": r.D.bit_length() - 1, "n_gates": r.ng, "n_vars": n_vars,
+           "n_inputs": int(info_out.n_inputs), "output_rows": [r.ng - 1],
+           "n_levels": {"outputs": int(info_out.n_levels), "given": int(info_in.n_levels)},
+           "plan_bytes": {"outputs": int(info_out.plan_bytes), "given": int(info_in.plan_bytes)},
+           "reps_each": reps, "interleaved": True, "warm_up_visits": {"outputs": 2, "given": 1},
+           "derived_root_equals_cpu_tree": bool(root_ok), "cpu_root_computed_before_proving": False,
+           "solution_passes_check_solved": True, "plan_same_on_every_build": bool(same_plans),
+           "all_proofs_equal": bool(all_equal), "proofs_compared": len(proofs) + 1,
+           "hbm_live_bytes_at_end": int(hbm),
+           "host_side_s": {"build_instance": round(r.build_s, 2), "cpu_poseidon_tree_afterwards": round(cpu_tree_s, 2),
+                           "preprocess": round(r.preprocess_s, 3)}}
+    for what in ("plan_build", "solve", "solve_and_prove"):
+        o, g = runs["outputs"][what], runs["given"][what]
+        out[what + "_s"] = {
+            "outputs_runs": [round(x, 5) for x in o], "given_runs": [round(x, 5) for x in g],
+            "outputs_median": round(median(o), 5), "given_median": round(median(g), 5),
+            "outputs_range": round(spread(o), 5), "given_range": round(spread(g), 5),
+            "median_difference": round(median(o) - median(g), 5),
+            "difference_exceeds_own_range": bool(median(o) - median(g) > max(spread(o), spread(g)))}
+    out["solve_stage_ms_median"] = {
+        name: {k: round(median([st[k] for st in runs[name]["stages"]]), 4) for k in runs[name]["stages"][0]
+               if k != "inputs_h2d_bytes"} for name in runs}
+    if not (all_equal and same_plans and root_ok):
+        raise SystemExit("solve_time: " + json.dumps({k: out[k] for k in (
+            "all_proofs_equal", "plan_same_on_every_build", "derived_root_equals_cpu_tree")}))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--height", type=int, default=15)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=15)
+    ap.add_argument("--outputs", action="store_true",
+                    help="the root row as an output of the plan, beside the present path (PI given)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    reps = max(args.reps, 5)
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "solve_outputs_time.json" if args.outputs else "solve_time.json")
+    if args.outputs:
+        return main_outputs(args, reps)
+
+    from pnp import abi
+    from pnp_testlib import R_MOD, fr_mont
+    r = setup(args, with_root=True)
+    ctx, ids, inputs, n_vars, root, root_var = r.ctx, r.ids, r.inputs, r.n_vars, r.root, r.root_var
+    height, ng, D, build_s, cpu_tree_s, preprocess_s = r.height, r.ng, r.D, r.build_s, r.cpu_tree_s, r.preprocess_s
+    pis = [(ng - 1, -root % R_MOD)]
 
     plan_s, infos = [], []
     for _ in range(3):

@@ -4,7 +4,8 @@
 // v1 gen_proof, which wraps them in the reference's contract, is v1.cpp.  The
 // satisfiability check (pnp_check_assignment, pnp_check_witness) is whole
 // here, over the kernels of check.hip, and so is the witness solver
-// (pnp_load_solve_inputs, pnp_solve_assignment) over those of solve.hip.
+// (pnp_load_solve_plan, pnp_solve_assignment, pnp_prove_solved) over those of
+// solve.hip.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -800,19 +801,40 @@ void solve_refuse_sharded(pnp_ctx *ctx, const char *what) {
 const pnp::ResidentKey::SolvePlan &solved_plan(pnp_ctx *ctx) {
     const pnp::ResidentKey::SolvePlan &sp = ctx->key.solve;
     if (!sp.loaded || !sp.solution.p) {
-        set_error("no solved assignment resident (pnp_load_solve_inputs and pnp_solve_assignment first)");
+        set_error("no solved assignment resident (a plan and pnp_solve_assignment first)");
         throw pnp::Error(PNP_E_NOKEY);
     }
     return sp;
 }
 
-}  // namespace
+// the caller's public inputs, none of them on an output row of the plan
+void refuse_pi_on_outputs(const pnp::ResidentKey::SolvePlan &sp, const char *what, uint64_t n_pi,
+                          const uint64_t *pi_pos) {
+    for (uint64_t k = 0; k < n_pi; k++)
+        if (sp.is_output(pi_pos[k])) {
+            set_error("%s: row %llu is an output of the plan (its public input is derived, not given)", what,
+                      (unsigned long long)pi_pos[k]);
+            throw pnp::Error(PNP_E_ARG);
+        }
+}
 
-extern "C" {
+// pos / canon: the caller's public inputs and then the derived ones of the resident solution
+void solved_pis(pnp_ctx *ctx, const char *what, uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
+                std::vector<uint64_t> &pos, std::vector<uint64_t> &canon) {
+    const pnp::ResidentKey::SolvePlan &sp = solved_plan(ctx);
+    refuse_pi_on_outputs(sp, what, n_pi, pi_pos);
+    pos.assign(pi_pos, pi_pos + n_pi);
+    canon.assign(pi_canon, pi_canon + 4 * n_pi);
+    pos.insert(pos.end(), sp.out_rows.begin(), sp.out_rows.end());
+    canon.insert(canon.end(), sp.out_canon.begin(), sp.out_canon.end());
+}
 
-int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, int device_ptrs,
-                          pnp_solve_info *info) {
-    if (!ctx || (n_inputs && !input_ids) || n_inputs > 0xffffffffULL) return PNP_E_ARG;
+// pnp_load_solve_plan, and pnp_load_solve_inputs (no outputs); `what` opens the messages
+int load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, uint64_t n_inputs,
+                    const uint64_t *output_rows, uint64_t n_outputs, int device_ptrs, pnp_solve_info *info) {
+    if (!ctx || (n_inputs && !input_ids) || n_inputs > 0xffffffffULL || (n_outputs && !output_rows) ||
+        n_outputs > 0xffffffffULL)
+        return PNP_E_ARG;
     PNP_TRY({
         using namespace pnp;
         if (info) {
@@ -825,7 +847,7 @@ int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_in
                                  : "prover key not loaded");
             throw Error(PNP_E_NOKEY);
         }
-        solve_refuse_sharded(ctx, "load solve inputs");
+        solve_refuse_sharded(ctx, what);
         tables_wait(ctx);  // (the NTT tables are shared with a background build)
         PNP_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
@@ -841,12 +863,12 @@ int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_in
         uint32_t err[2];
         solve_mark_inputs(ids.u32(), n_inputs, n_vars, level.u32(), err, small, s);
         if (err[0] != 0xffffffffu) {
-            set_error("load solve inputs: input id %u is not a variable (n_vars = %llu)", err[0],
+            set_error("%s: input id %u is not a variable (n_vars = %llu)", what, err[0],
                       (unsigned long long)n_vars);
             throw Error(PNP_E_ARG);
         }
         if (err[1] != 0xffffffffu) {
-            set_error("load solve inputs: input id %u is listed twice", err[1]);
+            set_error("%s: input id %u is listed twice", what, err[1]);
             throw Error(PNP_E_ARG);
         }
 
@@ -864,10 +886,27 @@ int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_in
         sel.q_4 = row_values(kQ4), sel.q_c = row_values(kQc), sel.q_hl = row_values(kQhl);
         sel.q_hr = row_values(kQhr), sel.q_h4 = row_values(kQh4), sel.q_arith = row_values(kQarith);
 
+        // the output rows: checked on the device, their rows marked for the mask
+        DevBuf out_rows, out_bits;
+        if (n_outputs) {
+            out_rows.alloc(8 * n_outputs);
+            out_bits.alloc(4 * ((ng + 31) / 32));
+            PNP_HIP(hipMemcpyAsync(out_rows.p, output_rows, 8 * n_outputs,
+                                   device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+            uint64_t oerr[3];
+            solve_mark_outputs(out_rows.u64(), n_outputs, ng, sel.q_arith, out_bits.u32(), oerr, small, s);
+            const char *const why[3] = {"is not a gate", "is listed twice", "has q_arith = 0"};
+            for (int k = 0; k < 3; k++)
+                if (oerr[k] != ~0ULL) {
+                    set_error("%s: output row %llu %s", what, (unsigned long long)oerr[k], why[k]);
+                    throw Error(PNP_E_ARG);
+                }
+        }
+
         const uint32_t *var = key.wm_var.u32();
         const uint32_t *dvar[4] = {var, var + ng, var + 2 * ng, var + 3 * ng};
         SolveBuild b;
-        solve_rounds(dvar, ng, n_vars, sel, level.u32(), def.u32(), b, s);
+        solve_rounds(dvar, ng, n_vars, sel, out_bits.u32(), level.u32(), def.u32(), b, s);
         pnp_solve_info out;
         memset(&out, 0, sizeof out);
         out.n_inputs = n_inputs;
@@ -880,17 +919,19 @@ int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_in
         out.first_undetermined = b.n_undetermined ? b.first_undetermined : ~0ULL;
         if (b.n_undetermined) {
             if (info) *info = out;
-            set_error("load solve inputs: variable %u is neither an input nor defined by an arithmetic row whose other "
+            set_error("%s: variable %u is neither an input nor defined by an arithmetic row whose other "
                       "wires are known (%llu such variables)",
-                      b.first_undetermined, (unsigned long long)b.n_undetermined);
+                      what, b.first_undetermined, (unsigned long long)b.n_undetermined);
             throw Error(PNP_E_ARG);
         }
 
         ResidentKey::SolvePlan &sp = key.solve;
-        sp.buf.alloc(SolveView::bytes(out.n_solved, out.n_levels, n_inputs, sel.q_m != nullptr));
-        sp.view.lay(sp.buf.p, out.n_solved, out.n_levels, sel.q_m != nullptr);
-        solve_emit(dvar, n_vars, sel, level.u32(), def.u32(), b, sp.view, s);
+        sp.buf.alloc(SolveView::bytes(out.n_solved, out.n_levels, n_inputs, n_outputs, sel.q_m != nullptr));
+        sp.view.lay(sp.buf.p, out.n_solved, out.n_levels, n_inputs, n_outputs, sel.q_m != nullptr);
+        solve_emit(dvar, n_vars, sel, level.u32(), def.u32(), b, out_rows.u64(), n_outputs, sp.view, s);
         if (n_inputs) PNP_HIP(hipMemcpyAsync(sp.view.ids, ids.p, 4 * n_inputs, hipMemcpyDeviceToDevice, s));
+        sp.out_rows.resize(n_outputs);
+        if (n_outputs) PNP_HIP(hipMemcpyAsync(sp.out_rows.data(), out_rows.p, 8 * n_outputs, hipMemcpyDeviceToHost, s));
         PNP_HIP(hipStreamSynchronize(s));
         // the launches: a level wider than a workgroup alone, narrower ones in runs
         uint64_t p = 0;
@@ -913,6 +954,20 @@ int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_in
     });
 }
 
+}  // namespace
+
+extern "C" {
+
+int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, int device_ptrs,
+                          pnp_solve_info *info) {
+    return load_solve_plan(ctx, "load solve inputs", input_ids, n_inputs, nullptr, 0, device_ptrs, info);
+}
+
+int pnp_load_solve_plan(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, const uint64_t *output_rows,
+                        uint64_t n_outputs, int device_ptrs, pnp_solve_info *info) {
+    return load_solve_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, device_ptrs, info);
+}
+
 int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs, uint64_t n_pi,
                          const uint64_t *pi_pos, const uint64_t *pi_canon) {
     if (!ctx || (n_inputs && !inputs) || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
@@ -924,7 +979,7 @@ int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs
         using namespace pnp;
         ResidentKey::SolvePlan &sp = ctx->key.solve;
         if (!sp.loaded) {
-            set_error("no solve plan resident (pnp_load_solve_inputs first)");
+            set_error("no solve plan resident (pnp_load_solve_inputs or pnp_load_solve_plan first)");
             throw Error(PNP_E_NOKEY);
         }
         if (n_inputs != sp.n_inputs) {
@@ -933,6 +988,7 @@ int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs
             throw Error(PNP_E_ARG);
         }
         solve_refuse_sharded(ctx, "solve assignment");
+        refuse_pi_on_outputs(sp, "solve assignment", n_pi, pi_pos);
         const ProveOpts opt{n_pi, pi_pos, pi_canon, nullptr};
         std::vector<uint64_t> pos;
         std::vector<Fr> val;
@@ -987,6 +1043,14 @@ int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs
         ctx->ktimer.end("solve_levels", s, e0, per_entry * (double)sp.n_solved);
         mark("solve_levels");
         ctx->ktimer.collect();
+        // the outputs: one launch after the last level, and their canonical values to the host
+        const uint64_t n_out = sp.out_rows.size();
+        sp.out_canon.assign(4 * n_out, 0);
+        if (n_out) {
+            k_solve_outputs(sp.view, n_out, vals, s);
+            PNP_HIP(hipMemcpyAsync(sp.out_canon.data(), sp.view.out.pi, 32 * n_out, hipMemcpyDeviceToHost, s));
+            mark("solve_outputs");
+        }
         ctx->stages.emplace_back("inputs_h2d_bytes", device_ptrs ? 0.0 : 32.0 * (double)n_inputs);
     });
 }
@@ -1027,6 +1091,51 @@ int pnp_assignment_values(pnp_ctx *ctx, const uint32_t *ids, uint64_t k, uint64_
         }
         PNP_HIP(hipStreamSynchronize(s));
     });
+}
+
+int pnp_solved_public_inputs(pnp_ctx *ctx, uint64_t *pos, uint64_t *canon, uint64_t cap, uint64_t *n) {
+    if (!ctx || !n || (cap && (!pos || !canon))) return PNP_E_ARG;
+    PNP_TRY({
+        const pnp::ResidentKey::SolvePlan &sp = solved_plan(ctx);
+        *n = sp.out_rows.size();
+        const uint64_t k = std::min<uint64_t>(cap, *n);
+        std::copy_n(sp.out_rows.begin(), k, pos);
+        std::copy_n(sp.out_canon.begin(), 4 * k, canon);
+    });
+}
+
+int pnp_prove_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon, const char *label,
+                     ProofC *out) {
+    if (!ctx || !out || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
+    std::vector<uint64_t> pos, canon;
+    uint64_t *values = nullptr;
+    uint64_t n_vars = 0;
+    const int rc = [&]() -> int {
+        PNP_TRY({
+            solved_pis(ctx, "prove solved", n_pi, pi_pos, pi_canon, pos, canon);
+            values = ctx->key.solve.solution.u64();
+            n_vars = ctx->key.wm_vars;
+        });
+    }();
+    if (rc != PNP_OK) return rc;
+    return pnp_prove_assignment(ctx, values, n_vars, 1, pos.size(), pos.data(), canon.data(), label, out);
+}
+
+int pnp_check_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
+                     pnp_check_report *report) {
+    if (!ctx || (n_pi && (!pi_pos || !pi_canon))) return PNP_E_ARG;
+    std::vector<uint64_t> pos, canon;
+    uint64_t *values = nullptr;
+    uint64_t n_vars = 0;
+    const int rc = [&]() -> int {
+        PNP_TRY({
+            solved_pis(ctx, "check solved", n_pi, pi_pos, pi_canon, pos, canon);
+            values = ctx->key.solve.solution.u64();
+            n_vars = ctx->key.wm_vars;
+        });
+    }();
+    if (rc != PNP_OK) return rc;
+    return pnp_check_assignment(ctx, values, n_vars, 1, pos.size(), pos.data(), canon.data(), report);
 }
 
 }  // extern "C"

@@ -368,14 +368,27 @@ struct SolveSel {
 // lvl_off[l + 1].  n entries; the arrays start 16-byte aligned.
 enum { kSolveQl, kSolveQr, kSolveQo, kSolveQ4, kSolveQhl, kSolveQhr, kSolveQh4, kSolveQc, kSolvePik, kSolveQm,
        kSolveCoefs };
+// The output rows of a plan, after the levels, in listed order: entry k derives
+//   PI_row = q_l' a + q_r' b + q_o' c + q_4' d + q_hl' a^5 + q_hr' b^5 + q_h4' d^5 + q_m' a b + q_c'
+// of row row[k], every q' the row's selector times -q_arith (every slot as it
+// stands: one that is not relevant only meets zero coefficients); there is no
+// pik (coef[kSolvePik] is nullptr).  pi: n_out Fr, the canonical values the
+// last solve derived.
+struct SolveOutView {
+    uint64_t *coef[kSolveCoefs];
+    uint32_t *row, *var[4];
+    uint64_t *pi;
+};
 struct SolveView {
     uint64_t *coef[kSolveCoefs];  // coef[kSolveQm] nullptr: the key has no q_m
     uint32_t *tgt, *row, *var[4], *lvl_off, *ids;
+    SolveOutView out;
     static uint64_t padded(uint64_t n) { return (n + 3) & ~3ULL; }
-    static uint64_t bytes(uint64_t n, uint64_t n_levels, uint64_t n_inputs, bool qm) {
-        return padded(n) * (32 * (kSolveCoefs - (qm ? 0 : 1)) + 4 * 6) + 4 * padded(n_levels + 1) + 4 * padded(n_inputs);
+    static uint64_t bytes(uint64_t n, uint64_t n_levels, uint64_t n_inputs, uint64_t n_out, bool qm) {
+        return padded(n) * (32 * (kSolveCoefs - (qm ? 0 : 1)) + 4 * 6) + 4 * padded(n_levels + 1) + 4 * padded(n_inputs) +
+               padded(n_out) * (32 * (kSolveCoefs - (qm ? 1 : 2)) + 4 * 5 + 32);
     }
-    void lay(void *base, uint64_t n, uint64_t n_levels, bool qm);
+    void lay(void *base, uint64_t n, uint64_t n_levels, uint64_t n_inputs, uint64_t n_out, bool qm);
 };
 // What the plan build leaves on the host: per level its width (the rounds of
 // include/pnp_plonk.h's plan rules), and what stayed undetermined.
@@ -388,15 +401,24 @@ struct SolveBuild {
 // lowest id >= n_vars in err[0], the lowest id listed twice in err[1] (~0: none)
 void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars, uint32_t *d_level, uint32_t err[2],
                        DevBuf &scratch, hipStream_t s);
+// The output rows: bit `row` of d_bits (n_gates bits, whole u32 words) set for
+// each of the n_out listed rows.  err[0]: the lowest listed row >= n_gates,
+// err[1]: the lowest row listed twice, err[2]: the lowest row whose q_arith is
+// zero (~0: none); the same on every run
+void solve_mark_outputs(const uint64_t *d_rows, uint64_t n_out, uint64_t n_gates, const uint64_t *q_arith,
+                        uint32_t *d_bits, uint64_t err[3], DevBuf &scratch, hipStream_t s);
 // the rounds: d_level[u] = the round that defines u (1-based), d_def[u] = 4 row
 // + slot of its defining row; d_level / d_def: n_vars u32, d_level as
-// solve_mark_inputs left it.  Synchronous (one read-back a round)
+// solve_mark_inputs left it.  A row of d_out_bits (solve_mark_outputs; nullptr:
+// no outputs) is never looked at.  Synchronous (one read-back a round)
 void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
-                  uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s);
+                  const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s);
 // the plan's entries in (level, variable id) order from d_level / d_def; the
-// inversions by k_batch_inverse.  `v` laid over a buffer of SolveView::bytes
+// inversions by k_batch_inverse; then the entries of the n_out output rows
+// d_out_rows.  `v` laid over a buffer of SolveView::bytes
 void solve_emit(const uint32_t *const d_var[4], uint64_t n_vars, const SolveSel &sel, const uint32_t *d_level,
-                const uint32_t *d_def, const SolveBuild &b, const SolveView &v, hipStream_t s);
+                const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows, uint64_t n_out,
+                const SolveView &v, hipStream_t s);
 // vals[ids[k]] = in[k]
 void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inputs, uint64_t *d_vals, hipStream_t s);
 // levels [l0, l1) of the plan: each level one launch when `wide`, else all of
@@ -404,6 +426,10 @@ void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inp
 // pi_pos / pi_val as CheckRows
 void k_solve_levels(const SolveView &v, uint32_t l0, uint32_t l1, uint64_t p0, uint64_t p1, bool wide, uint64_t *d_vals,
                     const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s);
+
+// the derived public inputs of the plan's n_out output rows from the solved
+// values: v.out.pi[k], canonical
+void k_solve_outputs(const SolveView &v, uint64_t n_out, const uint64_t *d_vals, hipStream_t s);
 
 void k_synth_merkle(int height, const uint64_t *pc_mont_host, const uint64_t *leaves, const uint64_t *blind,
                     uint64_t *nodes, uint64_t *const w[4], uint64_t *const sel[9], uint64_t *const sigma[4],

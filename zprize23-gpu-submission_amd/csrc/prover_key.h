@@ -193,15 +193,21 @@ struct ResidentKey {
         solve.drop();  // a plan is a schedule of this map's rows
     }
 
-    // ---- the witness solver's plan and solution (pnp_load_solve_inputs,
+    // ---- the witness solver's plan and solution (pnp_load_solve_plan,
     // pnp_solve_assignment; solve.hip) ----
-    // Built over the resident wire map for one choice of input variables;
-    // replaced by the next pnp_load_solve_inputs, dropped with the map
+    // Built over the resident wire map for one choice of input variables and
+    // output rows; replaced by the next pnp_load_solve_plan, dropped with the map
     struct SolvePlan {
         bool loaded = false;
         uint64_t n_inputs = 0, n_solved = 0, n_levels = 0;
-        DevBuf buf;      // the entries, the level offsets, the input ids (SolveView)
+        DevBuf buf;      // the entries, the level offsets, the input ids, the output entries (SolveView)
         SolveView view{};
+        // the output rows in listed order, and the public inputs the last solve
+        // derived for them (canonical, 4 words each; empty before a solve)
+        std::vector<uint64_t> out_rows, out_canon;
+        bool is_output(uint64_t row) const {
+            return std::find(out_rows.begin(), out_rows.end(), row) != out_rows.end();
+        }
         // the launches of a solve: one wide level (more than a workgroup), or a
         // run of consecutive levels that each fit one
         struct Run {
@@ -216,6 +222,8 @@ struct ResidentKey {
             n_inputs = n_solved = n_levels = 0;
             buf.release();
             runs.clear();
+            out_rows.clear();
+            out_canon.clear();
             solution.release();
         }
     } solve;

@@ -32,6 +32,13 @@
 // same workgroup: workgroup scope).  A slot that is not relevant may name a
 // variable that is not written yet: its coefficients are zero and the value
 // (zero: the buffer is cleared first) only ever meets a multiplication by them.
+//
+// Output rows (pnp_load_solve_plan): rows whose public input is derived, not
+// given.  k_solve_mark_outputs_ checks the list (atomicMin of the offending
+// row, a bitmap for the duplicates) and k_solve_mask_ gives their rows a zero
+// byte, so they never bid; k_solve_out_emit_ stores each row's selectors times
+// -q_arith after the level entries, and k_solve_outputs_, launched after the
+// last level, a lane a row, writes PI = -q_arith S in canonical form.
 // No LDS, no scalar-memory tricks; plain C++ and vector memory operations.
 #include "pnp_internal.h"
 
@@ -70,9 +77,29 @@ __device__ __forceinline__ uint32_t row_mask(const SolveSel &q, uint64_t i) {
     return r;
 }
 
-__global__ __launch_bounds__(256) void k_solve_mask_(SolveSel q, uint64_t n_gates, uint8_t *mask) {
+// (an output row's byte is zero from the start: no sweep ever looks at it)
+__global__ __launch_bounds__(256) void k_solve_mask_(SolveSel q, uint64_t n_gates, const uint32_t *out_bits,
+                                                     uint8_t *mask) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i < n_gates) mask[i] = (uint8_t)row_mask(q, i);
+    if (i >= n_gates) return;
+    const bool out = out_bits && ((out_bits[i >> 5] >> (i & 31)) & 1);
+    mask[i] = out ? (uint8_t)0 : (uint8_t)row_mask(q, i);
+}
+
+// a lane a listed output row: its bit, and the lowest row of each kind of mistake
+__global__ __launch_bounds__(256) void k_solve_mark_outputs_(const uint64_t *rows, uint64_t n_out, uint64_t n_gates,
+                                                             const uint64_t *q_arith, uint32_t *bits,
+                                                             unsigned long long *err) {
+    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (k >= n_out) return;
+    const uint64_t i = rows[k];
+    if (i >= n_gates) {
+        atomicMin(&err[0], (unsigned long long)i);
+        return;
+    }
+    const uint32_t bit = 1u << (i & 31);
+    if (atomicOr(&bits[i >> 5], bit) & bit) atomicMin(&err[1], (unsigned long long)i);
+    if (!nz(q_arith, i)) atomicMin(&err[2], (unsigned long long)i);
 }
 
 __global__ __launch_bounds__(256) void k_solve_inputs_(const uint32_t *ids, uint64_t n_inputs, uint64_t n_vars,
@@ -205,6 +232,28 @@ __global__ __launch_bounds__(256) void k_solve_fold_(SolveSel q, uint64_t n, Sol
     store_fr(v.coef[kSolvePik], p, neg(load_fr(den, n + p)));
 }
 
+// output entry k: its row and wires, and the row's selectors times -q_arith
+__global__ __launch_bounds__(256) void k_solve_out_emit_(MapArgs a, SolveSel q, const uint64_t *rows, uint64_t n_out,
+                                                         SolveOutView o) {
+    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (k >= n_out) return;
+    const uint64_t i = rows[k];
+    o.row[k] = (uint32_t)i;
+#pragma unroll
+    for (int j = 0; j < 4; j++) o.var[j][k] = a.var[j][i];
+    const Fr f = neg(load_fr(q.q_arith, i));
+    auto put = [&](int c, const uint64_t *col) { store_fr(o.coef[c], k, col ? load_fr(col, i) * f : Fr::zero()); };
+    put(kSolveQl, q.q_l);
+    put(kSolveQr, q.q_r);
+    put(kSolveQo, q.q_o);
+    put(kSolveQ4, q.q_4);
+    put(kSolveQhl, q.q_hl);
+    put(kSolveQhr, q.q_hr);
+    put(kSolveQh4, q.q_h4);
+    put(kSolveQc, q.q_c);
+    if (o.coef[kSolveQm]) put(kSolveQm, q.q_m);
+}
+
 __global__ __launch_bounds__(256) void k_solve_scatter_(const uint32_t *ids, const uint64_t *in, uint64_t n_inputs,
                                                         uint64_t *vals) {
     const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -252,9 +301,23 @@ __global__ __launch_bounds__(256) void k_solve_narrow_(SolveView v, uint32_t l0,
     }
 }
 
+// after the last level (stream order): a lane an output row, PI = -q_arith S in canonical form
+__global__ __launch_bounds__(256) void k_solve_outputs_(SolveOutView o, uint64_t n_out, const uint64_t *vals) {
+    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (k >= n_out) return;
+    const Fr a = load_fr(vals, o.var[0][k]), b = load_fr(vals, o.var[1][k]);
+    const Fr c = load_fr(vals, o.var[2][k]), d = load_fr(vals, o.var[3][k]);
+    Fr g = fr_mul2(load_fr(o.coef[kSolveQl], k), a, load_fr(o.coef[kSolveQr], k), b);
+    g += fr_mul2(load_fr(o.coef[kSolveQo], k), c, load_fr(o.coef[kSolveQ4], k), d);
+    g += fr_mul2(load_fr(o.coef[kSolveQhl], k), pow5(a), load_fr(o.coef[kSolveQhr], k), pow5(b));
+    g += load_fr(o.coef[kSolveQh4], k) * pow5(d) + load_fr(o.coef[kSolveQc], k);
+    if (o.coef[kSolveQm]) g += load_fr(o.coef[kSolveQm], k) * a * b;
+    store_fr(o.pi, k, from_mont(g));
+}
+
 }  // namespace
 
-void SolveView::lay(void *base, uint64_t n, uint64_t n_levels, bool qm) {
+void SolveView::lay(void *base, uint64_t n, uint64_t n_levels, uint64_t n_inputs, uint64_t n_out, bool qm) {
     const uint64_t nn = padded(n);
     uint64_t *w = static_cast<uint64_t *>(base);
     for (int c = 0; c < kSolveCoefs; c++) {
@@ -266,6 +329,29 @@ void SolveView::lay(void *base, uint64_t n, uint64_t n_levels, bool qm) {
     for (int j = 0; j < 4; j++) var[j] = h + (2 + j) * nn;
     lvl_off = h + 6 * nn;
     ids = lvl_off + padded(n_levels + 1);
+    // the output entries: Fr arrays first, so that they start 16-byte aligned
+    const uint64_t no = padded(n_out);
+    w = reinterpret_cast<uint64_t *>(ids + padded(n_inputs));
+    for (int c = 0; c < kSolveCoefs; c++) {
+        out.coef[c] = c == kSolvePik || (c == kSolveQm && !qm) ? nullptr : w;
+        if (out.coef[c]) w += 4 * no;
+    }
+    out.pi = w;
+    h = reinterpret_cast<uint32_t *>(w + 4 * no);
+    out.row = h;
+    for (int j = 0; j < 4; j++) out.var[j] = h + (1 + j) * no;
+}
+
+void solve_mark_outputs(const uint64_t *d_rows, uint64_t n_out, uint64_t n_gates, const uint64_t *q_arith,
+                        uint32_t *d_bits, uint64_t err[3], DevBuf &scratch, hipStream_t s) {
+    scratch.reserve(24);
+    PNP_HIP(hipMemsetAsync(scratch.p, 0xff, 24, s));
+    PNP_HIP(hipMemsetAsync(d_bits, 0, 4 * ((n_gates + 31) / 32), s));
+    hipLaunchKernelGGL(k_solve_mark_outputs_, dim3(nblk(n_out)), dim3(256), 0, s, d_rows, n_out, n_gates, q_arith,
+                       d_bits, static_cast<unsigned long long *>(scratch.p));
+    PNP_HIP(hipGetLastError());
+    PNP_HIP(hipMemcpyAsync(err, scratch.p, 24, hipMemcpyDeviceToHost, s));
+    PNP_HIP(hipStreamSynchronize(s));
 }
 
 void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars, uint32_t *d_level, uint32_t err[2],
@@ -283,12 +369,13 @@ void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars
 }
 
 void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
-                  uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s) {
+                  const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s) {
     const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
     DevBuf mask(n_gates), winner(4 * n_vars), ctr(8);
     uint8_t *d_mask = static_cast<uint8_t *>(mask.p);
     PNP_HIP(hipMemsetAsync(winner.p, 0xff, 4 * n_vars, s));
-    hipLaunchKernelGGL(k_solve_mask_, dim3(nblk(n_gates)), dim3(256), 0, s, sel, n_gates, d_mask);
+    hipLaunchKernelGGL(k_solve_mask_, dim3(nblk(n_gates)), dim3(256), 0, s, sel, n_gates, d_out_bits,
+                       d_mask);
     PNP_HIP(hipGetLastError());
     out.widths.clear();
     // (a round defines at least one variable, so there are at most n_vars of them)
@@ -316,14 +403,19 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
 }
 
 void solve_emit(const uint32_t *const d_var[4], uint64_t n_vars, const SolveSel &sel, const uint32_t *d_level,
-                const uint32_t *d_def, const SolveBuild &b, const SolveView &v, hipStream_t s) {
+                const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows, uint64_t n_out,
+                const SolveView &v, hipStream_t s) {
     const uint32_t n_levels = (uint32_t)b.widths.size();
     std::vector<uint32_t> off(n_levels + 1, 0);
     for (uint32_t l = 0; l < n_levels; l++) off[l + 1] = off[l] + b.widths[l];
     const uint64_t n = off[n_levels];
     PNP_HIP(hipMemcpyAsync(v.lvl_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, s));
+    const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
+    if (n_out) {  // products, not quotients: no inverse
+        hipLaunchKernelGGL(k_solve_out_emit_, dim3(nblk(n_out)), dim3(256), 0, s, a, sel, d_out_rows, n_out, v.out);
+        PNP_HIP(hipGetLastError());
+    }
     if (n) {
-        const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
         DevBuf keys(4 * n_vars), sort_scratch, den(64 * n), inv_scratch;
         hipLaunchKernelGGL(k_solve_keys_, dim3(nblk(n_vars)), dim3(256), 0, s, d_level, n_vars, n_levels, keys.u32());
         PNP_HIP(hipGetLastError());
@@ -343,6 +435,12 @@ void solve_emit(const uint32_t *const d_var[4], uint64_t n_vars, const SolveSel 
 void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inputs, uint64_t *d_vals, hipStream_t s) {
     if (!n_inputs) return;
     hipLaunchKernelGGL(k_solve_scatter_, dim3(nblk(n_inputs)), dim3(256), 0, s, d_ids, d_in, n_inputs, d_vals);
+    PNP_HIP(hipGetLastError());
+}
+
+void k_solve_outputs(const SolveView &v, uint64_t n_out, const uint64_t *d_vals, hipStream_t s) {
+    if (!n_out) return;
+    hipLaunchKernelGGL(k_solve_outputs_, dim3(nblk(n_out)), dim3(256), 0, s, v.out, n_out, d_vals);
     PNP_HIP(hipGetLastError());
 }
 

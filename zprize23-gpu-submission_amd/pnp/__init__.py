@@ -41,6 +41,7 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_load_wire_map", "pnp_gather_witness", "pnp_prove_assignment",
            "pnp_check_assignment", "pnp_check_witness",
            "pnp_load_solve_inputs", "pnp_solve_assignment", "pnp_assignment_ptr", "pnp_assignment_values",
+           "pnp_load_solve_plan", "pnp_solved_public_inputs", "pnp_prove_solved", "pnp_check_solved",
            "pnp_lde_blocks", "pnp_to_blocks", "pnp_intt_blocks", "pnp_t_combine_blocks", "pnp_t_combine_range")
 
 
@@ -319,6 +320,47 @@ class Context:
         check(self.lib.pnp_assignment_values(self.h, C.cast(arr, C.c_void_p) if ids is not None else None, k,
                                              C.cast(out, C.c_void_p)), "pnp_assignment_values")
         return [list(out[4 * j:4 * j + 4]) for j in range(k)]
+
+    # ---- public inputs the solve derives (output rows)
+    def load_solve_plan(self, ids: int, n_inputs: int, rows: int, n_outputs: int, device_ptrs: bool = False):
+        """pnp_load_solve_plan: load_solve_inputs with output rows; rows =
+        address (host, or HBM with device_ptrs, as ids) of n_outputs u64 row
+        indices.  Returns (rc, abi.SolveInfo) as load_solve_inputs."""
+        info = abi.SolveInfo()
+        rc = self.lib.pnp_load_solve_plan(self.h, C.c_void_p(ids or None), n_inputs, C.c_void_p(rows or None),
+                                          n_outputs, int(device_ptrs), C.byref(info))
+        if rc != -1:
+            check(rc, "pnp_load_solve_plan")
+        return rc, info
+
+    def solved_public_inputs(self):
+        """pnp_solved_public_inputs: [(row, canonical value int)] of the last
+        solve, in the order the plan lists its output rows."""
+        n = C.c_uint64()
+        check(self.lib.pnp_solved_public_inputs(self.h, None, None, 0, C.byref(n)), "pnp_solved_public_inputs")
+        k = n.value
+        pos = (C.c_uint64 * max(k, 1))()
+        vals = (C.c_uint64 * max(4 * k, 1))()
+        check(self.lib.pnp_solved_public_inputs(self.h, C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p), k,
+                                                C.byref(n)), "pnp_solved_public_inputs")
+        return [(pos[i], sum(vals[4 * i + j] << (64 * j) for j in range(4))) for i in range(k)]
+
+    def prove_solved(self, pis, label: bytes = None) -> abi.ProofC:
+        """pnp_prove_solved: prove the resident solution with pis (as
+        prove_ex) plus the derived public inputs; label None = the default."""
+        k, pos, vals = self._pi_args(list(pis))
+        out = abi.ProofC()
+        check(self.lib.pnp_prove_solved(self.h, k, C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p), label,
+                                        C.byref(out)), "pnp_prove_solved")
+        return out
+
+    def check_solved(self, pis):
+        """pnp_check_solved: check_assignment for the resident solution with
+        pis plus the derived public inputs.  Returns (ok, abi.CheckReport)."""
+        k, pos, vals = self._pi_args(list(pis))
+        rep = abi.CheckReport()
+        rc = self.lib.pnp_check_solved(self.h, k, C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p), C.byref(rep))
+        return self._checked(rc, rep, "pnp_check_solved")
 
     def last_error(self) -> str:
         msg = self.lib.pnp_last_error()

@@ -169,7 +169,17 @@ class SolveInfo(C.Structure):
 #   pnp_solve_assignment(ctx, inputs, n_inputs, device_ptrs, n_pi, pi_pos, pi_canon)
 #   pnp_assignment_ptr(ctx, &d_values, &n_vars)
 #   pnp_assignment_values(ctx, ids, k, out)
+# With output rows (public inputs the solve derives):
+#   pnp_load_solve_plan(ctx, input_ids, n_inputs, output_rows, n_outputs, device_ptrs, info)
+#   pnp_solved_public_inputs(ctx, pos, canon, cap, &n)
+#   pnp_prove_solved(ctx, n_pi, pi_pos, pi_canon, label, out)
+#   pnp_check_solved(ctx, n_pi, pi_pos, pi_canon, report)
 SOLVE_ARGTYPES = {
+    "pnp_load_solve_plan": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                            C.POINTER(SolveInfo)],
+    "pnp_solved_public_inputs": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
+    "pnp_prove_solved": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(ProofC)],
+    "pnp_check_solved": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(CheckReport)],
     "pnp_load_solve_inputs": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(SolveInfo)],
     "pnp_solve_assignment": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p],
     "pnp_assignment_ptr": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)],
