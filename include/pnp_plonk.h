@@ -628,6 +628,69 @@ int pnp_prove_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const 
 int pnp_check_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const uint64_t *pi_canon,
                      pnp_check_report *report /* may be NULL */);
 
+/* Range and logic rows that define: the quads from the accumulators.  Both
+ * families are deterministic base-4 decompositions, linked the way the
+ * reference's composer links them: every wire of a range row follows from the
+ * d wire of the next row, every wire of a logic row from the a and b wires of
+ * the next row.  A range_gate(x, 64) or a xor_gate / and_gate over values the
+ * circuit computes then needs no input beyond what defines x: range_gate ends
+ * with assert_equal(last accumulator, x), an arithmetic row that defines the
+ * last accumulator, and the chain unrolls upwards one row a round.  The
+ * reference's logic_gate leaves its last accumulators unlinked to its operands
+ * (INTEGRATION.md 4): list them as inputs or add the two assert_equal rows.
+ *
+ * pnp_load_solve_plan_gates is pnp_load_solve_plan with `gates`, the families
+ * whose rows may define (PNP_SOLVE_RANGE | PNP_SOLVE_LOGIC); pnp_load_solve_plan
+ * is this call with gates = 0: the same plan, info, plan_bytes, errors and
+ * solution.  A bit outside the two flags is PNP_E_ARG; a flag for a family
+ * whose selector the key does not have is accepted (there are no such rows).
+ * The rules join the ones above, in the same rounds; in round t every rule
+ * looks at K_(t-1):
+ *   RANGE (flag set): row i with range_selector[i] != 0, i + 1 < n_gates, not
+ *     an output row, is READY when the variable in slot d of row i + 1 is in
+ *     K_(t-1), and then bids for each of its slots a, b, c, d whose variable is
+ *     outside K_(t-1).  With V the canonical integer (0 <= V < r) of that
+ *     d_next:  a = V >> 2, b = V >> 4, c = V >> 6, d = V >> 8.  A slot whose
+ *     variable is known is not redefined: the composer's zero padding and
+ *     whatever is listed as input stay plain constraints, for pnp_check_*.
+ *   LOGIC (flag set): row i with logic_selector[i] != 0, q_c[i] = 1 (AND) or
+ *     -1 (XOR), i + 1 < n_gates, not an output row (a logic row with another
+ *     q_c is never ready), is READY when the variables in slots a and b of row
+ *     i + 1 are both in K_(t-1).  With A, B their canonical integers and op
+ *     the bitwise operation on the full integers it bids for whichever of
+ *     these five are outside K_(t-1):  a_i = A >> 2, b_i = B >> 2,
+ *     c_i = (A & 3) (B & 3), d_i = (A >> 2) op (B >> 2), and slot d of row
+ *     i + 1, d_(i+1) = A op B.  An XOR result is below 2^255 < 2 r and is
+ *     reduced with one conditional subtraction of r (the row's constraint then
+ *     fails, as it must for operands that were never in range): the solve
+ *     still inverts nothing and cannot fail.
+ *   TIES: among all bids of a round for one variable the least (row, role)
+ *     wins, the role order: the arithmetic slots a..d, range a..d, logic a, b,
+ *     c, d, d_next; the row is the row whose rule fires (for d_next: row i, not
+ *     i + 1).  This extends "the lowest row defines it" and keeps the plan the
+ *     same on every run.  Arithmetic rows behave as above, output rows never
+ *     bid, and a variable that nothing reaches is undetermined as above.
+ * Fixed-base and curve-addition rows (they would invert, and can fail) and
+ * lookup rows (a table search) still never define anything.
+ * A gate entry is 16 bytes (target, two sources, kind and shift) in arrays of
+ * their own beside the arithmetic entries, level order, by variable id within
+ * a level, with their own level offsets, all counted in plan_bytes; with
+ * gates = 0, or no such row defining anything, nothing is allocated for them.
+ * pnp_solve_info counts every entry of every kind in n_solved and max_width;
+ * pnp_solve_gate_entries: out[0], out[1] = the resident plan's entries defined
+ * by range rows, by logic rows (PNP_E_NOKEY without a plan).  Everything that
+ * takes a plan takes this one the same way: pnp_solve_assignment (a level is
+ * an arithmetic segment and a gate segment, more than 256 entries in all: its
+ * own launches, one a segment; solve_levels times and counts both),
+ * pnp_assignment_ptr / _values, pnp_solved_public_inputs, pnp_prove_solved,
+ * pnp_check_solved, pnp_hbm_usage, the drop and replace rules, and a sharded
+ * context is refused. */
+enum { PNP_SOLVE_RANGE = 1, PNP_SOLVE_LOGIC = 2 };
+int pnp_load_solve_plan_gates(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs,
+                              const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates,
+                              int device_ptrs, pnp_solve_info *info /* may be NULL */);
+int pnp_solve_gate_entries(pnp_ctx *ctx, uint64_t out[2]);
+
 /* Per-stage wall-clock (ms) of the last pnp_prove, for the bench/profiles.
  * Writes up to `cap` doubles and their names; returns the stage count. */
 int pnp_last_stage_times(pnp_ctx *ctx, double *ms, const char **names, int cap);

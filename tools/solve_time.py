@@ -32,7 +32,20 @@ the proof given the public input (here the derived one).  After two warm-up
 visits --reps visits of each path, interleaved; a visit is the plan build, a
 solve, and a solve + prove, each timed.  Afterwards the native tree is
 computed once and the derived root compared with it; every proof of both paths
-must be the same bytes."""
+must be the same bytes.
+
+    timeout -k 10 900 python tools/solve_time.py --gates [--out profiles/solve_gates_time.json]
+
+Range and logic rows that define (pnp_load_solve_plan_gates): a synthetic
+circuit of N 64-bit range checks of computed sums x = p + q and N / 2 64-bit
+XORs of pairs of those sums, laid out as the reference's composer lays
+range_gate and logic_gate (tests/gate_circuits.py), N chosen so that the domain
+is 2^20.  One unit (two sums, their range checks, one XOR: 57 rows) is built by
+the composer and tiled with numpy; the tiling is asserted to reproduce a
+three-unit composer circuit exactly.  The inputs are the p and q alone.
+Measured: the plan build (three times), the solve (--reps), the solve_levels
+kernels' own time, the entries by family and plan_bytes.  The solution must
+pass pnp_check_solved and hold the sums and the XORs Python computes."""
 import argparse
 import json
 import os
@@ -314,6 +327,146 @@ def main_outputs(args, reps):
     print(json.dumps(out))
 
 
+GATE_SELECTORS = SELECTORS + ("range_selector", "logic_selector")
+
+
+def gates_unit(cp, rng):
+    """Two sums x = p + q with range_of(x, 64) and the XOR of the two over 64
+    bits; returns ([p, q, p, q], [x, x], the result variable)."""
+    from gate_circuits import M1, logic_of, range_of
+    ins, xs = [], []
+    for _ in range(2):
+        p, q = cp.var(int(rng.integers(0, 1 << 62))), cp.var(int(rng.integers(0, 1 << 62)))
+        x = cp.var(cp.vals[p] + cp.vals[q])
+        cp.row({"q_arith": 1, "q_l": 1, "q_r": 1, "q_o": M1}, p, q, x, 0)
+        range_of(cp, x, 64)
+        ins += [p, q]
+        xs.append(x)
+    return ins, xs, logic_of(cp, xs[0], xs[1], 64, True)[1]
+
+
+def gates_circuit(units, tpl=None):
+    """(var (4, n_gates) u32, {selector: (n_gates, 4) Montgomery rows}, n_vars, input ids, [x ids], [result ids]):
+    from the composer itself (tpl None), or the one-unit template tiled."""
+    from circuits import Composer
+    from test_preprocess_ref import wire_map
+    if tpl is None:
+        cp = Composer(1)
+        rng = np.random.default_rng(1)
+        got = [gates_unit(cp, rng) for _ in range(units)]
+        cols = {name: mont_rows([r[0].get(name, 0) for r in cp.rows]) for name in GATE_SELECTORS}
+        assert not any(k not in GATE_SELECTORS for r in cp.rows for k in r[0])
+        return (wire_map(cp), cols, len(cp.vals), [0] + [v for g in got for v in g[0]], [v for g in got for v in g[1]],
+                [g[2] for g in got])
+    var1, cols1, n_vars1, ids1, xs1, res1 = tpl
+    per, rows = n_vars1 - 1, var1.shape[1]
+    shift = per * np.repeat(np.arange(units, dtype=np.int64), rows)
+    tiled = np.tile(var1.astype(np.int64), (1, units))
+    var = np.where(tiled == 0, 0, tiled + shift[None, :]).astype(np.uint32)
+    cols = {name: np.ascontiguousarray(np.tile(c, (units, 1))) for name, c in cols1.items()}
+    off = per * np.arange(units, dtype=np.int64)
+    spread_ids = lambda vs: (np.array(vs, dtype=np.int64)[None, :] + off[:, None]).reshape(-1)
+    ids = np.concatenate([[0], spread_ids(ids1[1:])])
+    return var, cols, 1 + per * units, ids, spread_ids(xs1), spread_ids(res1)
+
+
+def main_gates(args, reps):
+    from pnp import abi
+    from pnp_testlib import R_MOD, fr_mont, ints_to_arr
+    t0 = time.perf_counter()
+    tpl = gates_circuit(1)
+    rows_unit = tpl[0].shape[1]
+    want, got = gates_circuit(3), gates_circuit(3, tpl)
+    assert np.array_equal(want[0], got[0]) and want[2] == got[2] and list(want[3]) == list(got[3])
+    assert all(np.array_equal(want[1][k], got[1][k]) for k in GATE_SELECTORS)
+    assert list(want[4]) == list(got[4]) and list(want[5]) == list(got[5])
+    lg = args.lg
+    units = ((1 << lg) - 1) // rows_unit
+    var, cols, n_vars, ids, xs, res = gates_circuit(units, tpl)
+    ng = var.shape[1]
+    assert (1 << (lg - 1)) < ng < (1 << lg)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    rng = np.random.default_rng(args.seed)
+    vals = [0] + [int(v) for v in rng.integers(0, 1 << 62, size=len(ids) - 1)]
+    inputs = ints_to_arr([fr_mont(v) for v in vals])
+    sums = [vals[1 + 2 * k] + vals[2 + 2 * k] for k in range(2 * units)]
+    xors = [sums[2 * k] ^ sums[2 * k + 1] for k in range(units)]
+    build_s = time.perf_counter() - t0
+
+    import torch
+    import pnp
+    if not torch.cuda.is_available():
+        raise SystemExit("solve_time: no GPU (a measurement needs one; nothing is written)")
+    desc = abi.CircuitDesc(n_gates=ng, n_vars=n_vars, lookup_len=0)
+    var = np.ascontiguousarray(var)
+    for j in range(4):
+        desc.var[j] = var[j].ctypes.data_as(abi.U32P)
+    for k, name in enumerate(abi.DESC_SELECTORS):
+        if name in cols and cols[name].any():
+            desc.sel[k] = cols[name].ctypes.data_as(abi.U64P)
+    ctx = pnp.Context(0)
+    t0 = time.perf_counter()
+    ctx.preprocess(desc, device_ptrs=False)
+    preprocess_s = time.perf_counter() - t0
+
+    plan_s, infos = [], []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        rc, info = ctx.load_solve_plan_gates(ids.ctypes.data, len(ids), 0, 0, abi.SOLVE_RANGE | abi.SOLVE_LOGIC, False)
+        plan_s.append(time.perf_counter() - t0)
+        if rc != 0:
+            raise SystemExit(f"solve_time: no plan: {ctx.last_error()}")
+        infos.append(bytes(info))
+    if len(set(infos)) != 1 or info.n_solved + info.n_inputs != n_vars:
+        raise SystemExit("solve_time: the plan differs between builds, or does not cover every variable")
+    n_range, n_logic = ctx.solve_gate_entries()
+
+    def solve():
+        t0 = time.perf_counter()
+        ctx.solve_assignment(inputs.ctypes.data, len(ids), False)
+        return time.perf_counter() - t0, dict(ctx.stage_times())
+
+    solve()
+    ok, rep = ctx.check_solved([])
+    if not ok:
+        raise SystemExit(f"solve_time: the solution fails the check: {ctx.last_error()}")
+    to_int = lambda limbs: sum(int(w) << (64 * k) for k, w in enumerate(limbs))
+    probe = sorted(set(range(0, units, max(1, units // 64))) | {units - 1})
+    got_x = [to_int(l) for l in ctx.assignment_values(ids=[int(xs[2 * k]) for k in probe])]
+    got_r = [to_int(l) for l in ctx.assignment_values(ids=[int(res[k]) for k in probe])]
+    if got_x != [fr_mont(sums[2 * k]) for k in probe] or got_r != [fr_mont(xors[k]) for k in probe]:
+        raise SystemExit("solve_time: the solved sums or XORs are not Python's")
+    runs = [solve() for _ in range(reps)]
+    ctx.kernel_timing(True)
+    solve()
+    levels_ms, _ = ctx.kernel_stats("solve_levels")
+    levels_bytes = ctx.kernel_bytes("solve_levels")
+    ctx.kernel_timing(False)
+    hbm = ctx.hbm_usage()["live"]
+    ctx.close()
+    out = {
+        "circuit": "N sums x = p + q with range_gate(x, 64), N / 2 xor_gate(x, x', 64), composer layout",
+        "lg": lg, "n_gates": ng, "n_vars": n_vars, "range_checks": 2 * units, "xors": units,
+        "n_inputs": int(info.n_inputs), "n_solved": int(info.n_solved), "n_levels": int(info.n_levels),
+        "max_width": int(info.max_width), "entries": {"arithmetic": int(info.n_solved) - n_range - n_logic,
+                                                     "range": int(n_range), "logic": int(n_logic)},
+        "plan_bytes": int(info.plan_bytes), "tiling_reproduces_the_composer": True,
+        "solution_passes_check_solved": True, "sums_and_xors_probed": len(probe), "plan_same_on_every_build": True,
+        "plan_build_s_runs": [round(x, 4) for x in plan_s], "plan_build_s": round(median(plan_s), 4),
+        "solve_s_runs": [round(t, 5) for t, _ in runs], "solve_s": round(median([t for t, _ in runs]), 5),
+        "solve_stage_ms_median": {k: round(median([st[k] for _, st in runs]), 4) for k in ("solve_inputs", "solve_levels")},
+        "levels_kernels_ms": round(levels_ms, 4), "levels_kernels_bytes": int(levels_bytes),
+        "levels_kernels_gb_s": round(levels_bytes / (levels_ms * 1e-3) / 1e9, 1) if levels_ms > 0 else None,
+        "reps": reps, "hbm_live_bytes_at_end": int(hbm),
+        "host_side_s": {"build_instance": round(build_s, 2), "preprocess": round(preprocess_s, 3)},
+    }
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=15)
@@ -321,11 +474,17 @@ def main():
     ap.add_argument("--seed", type=int, default=15)
     ap.add_argument("--outputs", action="store_true",
                     help="the root row as an output of the plan, beside the present path (PI given)")
+    ap.add_argument("--gates", action="store_true",
+                    help="range and logic rows that define: a synthetic circuit of range checks and XORs on 2^lg")
+    ap.add_argument("--lg", type=int, default=20, help="--gates: the domain")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     reps = max(args.reps, 5)
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "solve_outputs_time.json" if args.outputs else "solve_time.json")
+        name = "solve_gates_time.json" if args.gates else "solve_outputs_time.json" if args.outputs else "solve_time.json"
+        args.out = os.path.join(REPO, "profiles", name)
+    if args.gates:
+        return main_gates(args, reps)
     if args.outputs:
         return main_outputs(args, reps)
 

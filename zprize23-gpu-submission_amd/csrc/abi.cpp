@@ -829,12 +829,18 @@ void solved_pis(pnp_ctx *ctx, const char *what, uint64_t n_pi, const uint64_t *p
     canon.insert(canon.end(), sp.out_canon.begin(), sp.out_canon.end());
 }
 
-// pnp_load_solve_plan, and pnp_load_solve_inputs (no outputs); `what` opens the messages
+// pnp_load_solve_plan_gates, pnp_load_solve_plan (no gate families) and
+// pnp_load_solve_inputs (no outputs either); `what` opens the messages
 int load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, uint64_t n_inputs,
-                    const uint64_t *output_rows, uint64_t n_outputs, int device_ptrs, pnp_solve_info *info) {
+                    const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, int device_ptrs,
+                    pnp_solve_info *info) {
     if (!ctx || (n_inputs && !input_ids) || n_inputs > 0xffffffffULL || (n_outputs && !output_rows) ||
         n_outputs > 0xffffffffULL)
         return PNP_E_ARG;
+    if (gates & ~(uint32_t)(PNP_SOLVE_RANGE | PNP_SOLVE_LOGIC)) {
+        set_error("%s: gates = 0x%x has a bit that is no gate family (PNP_SOLVE_RANGE | PNP_SOLVE_LOGIC)", what, gates);
+        return PNP_E_ARG;
+    }
     PNP_TRY({
         using namespace pnp;
         if (info) {
@@ -854,6 +860,10 @@ int load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, u
         key.solve.drop();
         const uint64_t D = key.n, ng = key.wm_gates, n_vars = key.wm_vars;
         const uint32_t lg = log2_exact(D);
+        if (ng >= (1ULL << 28)) {  // a bid is 16 row + role in 32 bits
+            set_error("%s: %llu gates (a plan covers fewer than 2^28)", what, (unsigned long long)ng);
+            throw Error(PNP_E_ARG);
+        }
 
         // the input ids, and every variable's level: 0 for an input
         DevBuf ids(4 * std::max<uint64_t>(n_inputs, 1)), level(4 * n_vars), def(4 * n_vars), small;
@@ -885,6 +895,9 @@ int load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, u
         sel.q_m = row_values(kQm), sel.q_l = row_values(kQl), sel.q_r = row_values(kQr), sel.q_o = row_values(kQo);
         sel.q_4 = row_values(kQ4), sel.q_c = row_values(kQc), sel.q_hl = row_values(kQhl);
         sel.q_hr = row_values(kQhr), sel.q_h4 = row_values(kQh4), sel.q_arith = row_values(kQarith);
+        // (a family's rows: only where its flag is set and the key has the selector)
+        if (gates & PNP_SOLVE_RANGE) sel.range = row_values(kRange);
+        if (gates & PNP_SOLVE_LOGIC) sel.logic = row_values(kLogic);
 
         // the output rows: checked on the device, their rows marked for the mask
         DevBuf out_rows, out_bits;
@@ -911,45 +924,59 @@ int load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, u
         memset(&out, 0, sizeof out);
         out.n_inputs = n_inputs;
         out.n_levels = b.widths.size();
-        for (uint32_t w : b.widths) {
-            out.n_solved += w;
-            out.max_width = std::max<uint64_t>(out.max_width, w);
+        uint64_t n_arith = 0, n_gate = 0;
+        for (size_t l = 0; l < b.widths.size(); l++) {
+            n_arith += b.widths[l];
+            n_gate += b.gate_widths[l];
+            out.max_width = std::max<uint64_t>(out.max_width, (uint64_t)b.widths[l] + b.gate_widths[l]);
         }
+        out.n_solved = n_arith + n_gate;
         out.n_undetermined = b.n_undetermined;
         out.first_undetermined = b.n_undetermined ? b.first_undetermined : ~0ULL;
         if (b.n_undetermined) {
             if (info) *info = out;
-            set_error("%s: variable %u is neither an input nor defined by an arithmetic row whose other "
-                      "wires are known (%llu such variables)",
+            set_error(gates ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other "
+                              "wires are known, nor by a range or logic row whose next row is (%llu such variables)"
+                            : "%s: variable %u is neither an input nor defined by an arithmetic row whose other "
+                              "wires are known (%llu such variables)",
                       what, b.first_undetermined, (unsigned long long)b.n_undetermined);
             throw Error(PNP_E_ARG);
         }
 
         ResidentKey::SolvePlan &sp = key.solve;
-        sp.buf.alloc(SolveView::bytes(out.n_solved, out.n_levels, n_inputs, n_outputs, sel.q_m != nullptr));
-        sp.view.lay(sp.buf.p, out.n_solved, out.n_levels, n_inputs, n_outputs, sel.q_m != nullptr);
-        solve_emit(dvar, n_vars, sel, level.u32(), def.u32(), b, out_rows.u64(), n_outputs, sp.view, s);
+        sp.buf.alloc(SolveView::bytes(n_arith, out.n_levels, n_inputs, n_outputs, sel.q_m != nullptr));
+        sp.view.lay(sp.buf.p, n_arith, out.n_levels, n_inputs, n_outputs, sel.q_m != nullptr);
+        if (n_gate) {
+            sp.gate_buf.alloc(SolveGateView::bytes(n_gate, out.n_levels));
+            sp.gate_view.lay(sp.gate_buf.p, n_gate);
+        }
+        solve_emit(dvar, ng, n_vars, sel, level.u32(), def.u32(), b, out_rows.u64(), n_outputs, sp.view, sp.gate_view,
+                   s);
         if (n_inputs) PNP_HIP(hipMemcpyAsync(sp.view.ids, ids.p, 4 * n_inputs, hipMemcpyDeviceToDevice, s));
         sp.out_rows.resize(n_outputs);
         if (n_outputs) PNP_HIP(hipMemcpyAsync(sp.out_rows.data(), out_rows.p, 8 * n_outputs, hipMemcpyDeviceToHost, s));
         PNP_HIP(hipStreamSynchronize(s));
-        // the launches: a level wider than a workgroup alone, narrower ones in runs
-        uint64_t p = 0;
+        // the launches: a level wider than a workgroup (both segments counted) alone, narrower ones in runs
+        uint64_t p = 0, g = 0;
         for (uint32_t l = 0; l < b.widths.size(); l++) {
-            const bool wide = b.widths[l] > 256;
+            const uint64_t wa = b.widths[l], wg = b.gate_widths[l];
+            const bool wide = wa + wg > 256;
             if (!wide && !sp.runs.empty() && !sp.runs.back().wide) {
                 sp.runs.back().l1 = l + 1;
-                sp.runs.back().p1 = p + b.widths[l];
+                sp.runs.back().p1 = p + wa;
+                sp.runs.back().g1 = g + wg;
             } else {
-                sp.runs.push_back({l, l + 1, p, p + b.widths[l], wide});
+                sp.runs.push_back({l, l + 1, p, p + wa, g, g + wg, wide});
             }
-            p += b.widths[l];
+            p += wa;
+            g += wg;
         }
+        sp.n_range = b.n_range, sp.n_logic = b.n_logic, sp.n_two = b.n_two;
         sp.n_inputs = n_inputs;
         sp.n_solved = out.n_solved;
         sp.n_levels = out.n_levels;
         sp.loaded = true;
-        out.plan_bytes = sp.buf.bytes;
+        out.plan_bytes = sp.buf.bytes + sp.gate_buf.bytes;
         if (info) *info = out;
     });
 }
@@ -960,12 +987,31 @@ extern "C" {
 
 int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, int device_ptrs,
                           pnp_solve_info *info) {
-    return load_solve_plan(ctx, "load solve inputs", input_ids, n_inputs, nullptr, 0, device_ptrs, info);
+    return load_solve_plan(ctx, "load solve inputs", input_ids, n_inputs, nullptr, 0, 0, device_ptrs, info);
 }
 
 int pnp_load_solve_plan(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, const uint64_t *output_rows,
                         uint64_t n_outputs, int device_ptrs, pnp_solve_info *info) {
-    return load_solve_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, device_ptrs, info);
+    return load_solve_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, 0, device_ptrs, info);
+}
+
+int pnp_load_solve_plan_gates(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, const uint64_t *output_rows,
+                              uint64_t n_outputs, uint32_t gates, int device_ptrs, pnp_solve_info *info) {
+    return load_solve_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, gates, device_ptrs,
+                           info);
+}
+
+int pnp_solve_gate_entries(pnp_ctx *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return PNP_E_ARG;
+    PNP_TRY({
+        const pnp::ResidentKey::SolvePlan &sp = ctx->key.solve;
+        if (!sp.loaded) {
+            set_error("no solve plan resident (pnp_load_solve_plan_gates first)");
+            throw pnp::Error(PNP_E_NOKEY);
+        }
+        out[0] = sp.n_range;
+        out[1] = sp.n_logic;
+    });
 }
 
 int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs, uint64_t n_pi,
@@ -1036,11 +1082,23 @@ int pnp_solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs
 
         hipEvent_t e0 = nullptr;
         ctx->ktimer.begin("solve_levels", s, e0);
-        for (const auto &r : sp.runs)
-            k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, r.wide, vals, d_pos, d_val, (uint32_t)pos.size(), s);
-        // an entry reads its coefficients and ids, four values, and writes one
+        for (const auto &r : sp.runs) {
+            if (r.g1 == r.g0) {  // no gate entries: the arithmetic kernels alone
+                k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, r.wide, vals, d_pos, d_val, (uint32_t)pos.size(), s);
+            } else if (r.wide) {  // one level, a launch a segment
+                if (r.p1 > r.p0)
+                    k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, true, vals, d_pos, d_val, (uint32_t)pos.size(), s);
+                k_solve_gate_level(sp.gate_view, r.g0, r.g1, vals, s);
+            } else {
+                k_solve_mixed_levels(sp.view, sp.gate_view, r.l0, r.l1, vals, d_pos, d_val, (uint32_t)pos.size(), s);
+            }
+        }
+        // an entry reads its coefficients and ids, four values, and writes one;
+        // a gate entry reads its 16 bytes and one or two values, and writes one
         const double per_entry = 32.0 * (kSolveCoefs - (sp.view.coef[kSolveQm] ? 1 : 2)) + 4 * 6 + 32 * 5;
-        ctx->ktimer.end("solve_levels", s, e0, per_entry * (double)sp.n_solved);
+        const uint64_t n_gate = sp.n_range + sp.n_logic;
+        ctx->ktimer.end("solve_levels", s, e0,
+                        per_entry * (double)(sp.n_solved - n_gate) + 80.0 * (double)n_gate + 32.0 * (double)sp.n_two);
         mark("solve_levels");
         ctx->ktimer.collect();
         // the outputs: one launch after the last level, and their canonical values to the host

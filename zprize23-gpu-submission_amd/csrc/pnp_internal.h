@@ -359,6 +359,9 @@ void k_check_copy(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
 // the selector rows the plan is built from: D rows each, HBM; q_m nullptr = zero
 struct SolveSel {
     const uint64_t *q_m, *q_l, *q_r, *q_o, *q_4, *q_c, *q_hl, *q_hr, *q_h4, *q_arith;
+    // the gate families of pnp_load_solve_plan_gates: nullptr = the family's
+    // flag is not set, or the key has no such rows
+    const uint64_t *range, *logic;
 };
 // A plan in HBM, level order: entry p defines variable tgt[p] from row row[p] as
 //   q_l' a + q_r' b + q_o' c + q_4' d + q_hl' a^5 + q_hr' b^5 + q_h4' d^5 + q_m' a b + q_c' + pik PI_row,
@@ -393,10 +396,36 @@ struct SolveView {
 // What the plan build leaves on the host: per level its width (the rounds of
 // include/pnp_plonk.h's plan rules), and what stayed undetermined.
 struct SolveBuild {
-    std::vector<uint32_t> widths;
+    std::vector<uint32_t> widths;  // arithmetic entries of each level
+    std::vector<uint32_t> gate_widths;  // gate entries of each level (as many levels; all zero without gate rows)
+    uint64_t n_range = 0, n_logic = 0;  // gate entries by the family of the row that defines them
+    uint64_t n_two = 0;                 // gate entries that read two values (the others read one)
     uint64_t n_undetermined = 0;
     uint32_t first_undetermined = 0xffffffffu;
 };
+// The gate entries of a plan (range and logic rows), in arrays of their own,
+// level order, by variable id within a level: entry g defines variable tgt[g]
+// from the canonical integers A, B of the variables a[g], b[g] (b = a where
+// only one is read); word[g] = kind | shift << 8:
+//   kSolveGateShift  A >> shift          (every range slot; logic a_i, b_i)
+//   kSolveGateProd   (A & 3) (B & 3)     (logic c_i)
+//   kSolveGateAnd    (A >> shift) & (B >> shift)
+//   kSolveGateXor    (A >> shift) ^ (B >> shift), minus r when that reaches r
+// Level l is entries lvl_off[l] .. lvl_off[l + 1].
+enum { kSolveGateShift, kSolveGateProd, kSolveGateAnd, kSolveGateXor };
+struct SolveGateView {
+    uint32_t *tgt, *a, *b, *word, *lvl_off;
+    static uint64_t bytes(uint64_t n, uint64_t n_levels) {
+        return 16 * SolveView::padded(n) + 4 * SolveView::padded(n_levels + 1);
+    }
+    void lay(void *base, uint64_t n) {
+        const uint64_t nn = SolveView::padded(n);
+        tgt = static_cast<uint32_t *>(base), a = tgt + nn, b = tgt + 2 * nn, word = tgt + 3 * nn, lvl_off = tgt + 4 * nn;
+    }
+};
+// The (row, role) of a bid and of a definition: 16 row + role, the least wins.
+// Roles: the arithmetic slots a..d, then range a..d, then logic a, b, c, d, d_next
+enum { kSolveRoleRange = 4, kSolveRoleLogic = 8, kSolveRoles = 13 };
 // level[u] = 0 for the n_inputs listed variables (UNSET before); returns the
 // lowest id >= n_vars in err[0], the lowest id listed twice in err[1] (~0: none)
 void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars, uint32_t *d_level, uint32_t err[2],
@@ -407,18 +436,21 @@ void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars
 // zero (~0: none); the same on every run
 void solve_mark_outputs(const uint64_t *d_rows, uint64_t n_out, uint64_t n_gates, const uint64_t *q_arith,
                         uint32_t *d_bits, uint64_t err[3], DevBuf &scratch, hipStream_t s);
-// the rounds: d_level[u] = the round that defines u (1-based), d_def[u] = 4 row
-// + slot of its defining row; d_level / d_def: n_vars u32, d_level as
-// solve_mark_inputs left it.  A row of d_out_bits (solve_mark_outputs; nullptr:
-// no outputs) is never looked at.  Synchronous (one read-back a round)
+// the rounds: d_level[u] = the round that defines u (1-based), d_def[u] = 16 row
+// + role of the rule that defines it (row: the row whose rule fires); d_level /
+// d_def: n_vars u32, d_level as solve_mark_inputs left it.  A row of d_out_bits
+// (solve_mark_outputs; nullptr: no outputs) is never looked at.  sel.range /
+// sel.logic switch the gate rules on (n_gates < 2^28).  Synchronous (one
+// read-back a round)
 void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
                   const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s);
 // the plan's entries in (level, variable id) order from d_level / d_def; the
 // inversions by k_batch_inverse; then the entries of the n_out output rows
-// d_out_rows.  `v` laid over a buffer of SolveView::bytes
-void solve_emit(const uint32_t *const d_var[4], uint64_t n_vars, const SolveSel &sel, const uint32_t *d_level,
-                const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows, uint64_t n_out,
-                const SolveView &v, hipStream_t s);
+// d_out_rows.  `v` laid over a buffer of SolveView::bytes; `g` (read only when
+// the build has gate entries) over one of SolveGateView::bytes
+void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
+                const uint32_t *d_level, const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows,
+                uint64_t n_out, const SolveView &v, const SolveGateView &g, hipStream_t s);
 // vals[ids[k]] = in[k]
 void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inputs, uint64_t *d_vals, hipStream_t s);
 // levels [l0, l1) of the plan: each level one launch when `wide`, else all of
@@ -426,6 +458,14 @@ void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inp
 // pi_pos / pi_val as CheckRows
 void k_solve_levels(const SolveView &v, uint32_t l0, uint32_t l1, uint64_t p0, uint64_t p1, bool wide, uint64_t *d_vals,
                     const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s);
+
+// the gate entries g0 .. g1 - 1 of one level, a lane an entry
+void k_solve_gate_level(const SolveGateView &g, uint64_t g0, uint64_t g1, uint64_t *d_vals, hipStream_t s);
+// levels [l0, l1) with gate entries among them, every level at most 256 entries
+// in all: one launch of one workgroup of 512, the arithmetic entries of a level
+// in its first four waves and the gate entries in the other four
+void k_solve_mixed_levels(const SolveView &v, const SolveGateView &g, uint32_t l0, uint32_t l1, uint64_t *d_vals,
+                          const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s);
 
 // the derived public inputs of the plan's n_out output rows from the solved
 // values: v.out.pi[k], canonical

@@ -202,17 +202,23 @@ struct ResidentKey {
         uint64_t n_inputs = 0, n_solved = 0, n_levels = 0;
         DevBuf buf;      // the entries, the level offsets, the input ids, the output entries (SolveView)
         SolveView view{};
+        // the entries range and logic rows define (pnp_load_solve_plan_gates), in
+        // arrays of their own; empty when the plan has none
+        DevBuf gate_buf;
+        SolveGateView gate_view{};
+        uint64_t n_range = 0, n_logic = 0, n_two = 0;  // by family; n_two: those reading two values
         // the output rows in listed order, and the public inputs the last solve
         // derived for them (canonical, 4 words each; empty before a solve)
         std::vector<uint64_t> out_rows, out_canon;
         bool is_output(uint64_t row) const {
             return std::find(out_rows.begin(), out_rows.end(), row) != out_rows.end();
         }
-        // the launches of a solve: one wide level (more than a workgroup), or a
+        // the launches of a solve: one wide level (more than a workgroup,
+        // arithmetic entries p0 .. p1 and gate entries g0 .. g1 together), or a
         // run of consecutive levels that each fit one
         struct Run {
             uint32_t l0, l1;
-            uint64_t p0, p1;
+            uint64_t p0, p1, g0, g1;
             bool wide;
         };
         std::vector<Run> runs;
@@ -220,7 +226,9 @@ struct ResidentKey {
         void drop() {
             loaded = false;
             n_inputs = n_solved = n_levels = 0;
+            n_range = n_logic = n_two = 0;
             buf.release();
+            gate_buf.release();
             runs.clear();
             out_rows.clear();
             out_canon.clear();

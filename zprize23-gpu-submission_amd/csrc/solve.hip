@@ -13,9 +13,9 @@
 //   k_solve_ready_   round t, a lane a row not yet finished: the relevant slots
 //                    whose variable is unknown; none left: the row is finished
 //                    (its byte is cleared); exactly one, solvable: the row
-//                    bids for it, atomicMin of the row on winner[u]
+//                    bids for it, atomicMin of 16 row + slot on winner[u]
 //   k_solve_commit_  the same rows again: the bidder that holds winner[u]
-//                    defines u (level[u] = t, def[u] = 4 row + slot).  "Known"
+//                    defines u (level[u] = t, def[u] = 16 row + slot).  "Known"
 //                    is level[u] < t here, so the levels written by other
 //                    lanes of this launch change nothing any lane decides
 //   the variables are then sorted by level (preprocess.hip's stable radix
@@ -39,6 +39,17 @@
 // byte, so they never bid; k_solve_out_emit_ stores each row's selectors times
 // -q_arith after the level entries, and k_solve_outputs_, launched after the
 // last level, a lane a row, writes PI = -q_arith S in canonical form.
+//
+// Range and logic rows (pnp_load_solve_plan_gates): a second byte a row
+// (k_solve_mask_) says which gate rules the row still has; a ready gate row
+// bids for up to five variables, one of them in the next row, so a bid and a
+// definition are 16 row + role (atomicMin: the least (row, role) wins) and the
+// commit counts what each family defined.  Their entries (16 bytes: target, two
+// sources, kind and shift; k_solve_gate_emit_) live in arrays of their own, and
+// run in lanes of their own: k_solve_gate_wide_ a lane an entry of one level,
+// k_solve_mixed_ one workgroup of 512 over a run of narrow levels, arithmetic
+// entries in waves 0-3 and gate entries in waves 4-7, so that no wave runs both
+// bodies.  Plans without gate entries launch what they always launched.
 // No LDS, no scalar-memory tricks; plain C++ and vector memory operations.
 #include "pnp_internal.h"
 
@@ -77,13 +88,28 @@ __device__ __forceinline__ uint32_t row_mask(const SolveSel &q, uint64_t i) {
     return r;
 }
 
-// (an output row's byte is zero from the start: no sweep ever looks at it)
+// the gate rules of row i: kGateRange, kGateLogic (with kGateXor: q_c = -1, else
+// q_c = 1; a logic row with another q_c has no rule), none on the last row
+enum : uint32_t { kGateRange = 1, kGateLogic = 2, kGateXor = 4 };
+__device__ __forceinline__ uint32_t row_gates(const SolveSel &q, uint64_t i, uint64_t n_gates) {
+    if (i + 1 >= n_gates) return 0;
+    uint32_t r = nz(q.range, i) ? kGateRange : 0;
+    if (nz(q.logic, i)) {
+        const Fr c = load_fr(q.q_c, i);
+        if (c == Fr::one()) r |= kGateLogic;
+        else if (c == neg(Fr::one())) r |= kGateLogic | kGateXor;
+    }
+    return r;
+}
+
+// (an output row's bytes are zero from the start: no sweep ever looks at it)
 __global__ __launch_bounds__(256) void k_solve_mask_(SolveSel q, uint64_t n_gates, const uint32_t *out_bits,
-                                                     uint8_t *mask) {
+                                                     uint8_t *mask, uint8_t *gmask) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (i >= n_gates) return;
     const bool out = out_bits && ((out_bits[i >> 5] >> (i & 31)) & 1);
     mask[i] = out ? (uint8_t)0 : (uint8_t)row_mask(q, i);
+    if (gmask) gmask[i] = out ? (uint8_t)0 : (uint8_t)row_gates(q, i, n_gates);
 }
 
 // a lane a listed output row: its bit, and the lowest row of each kind of mistake
@@ -128,41 +154,97 @@ __device__ __forceinline__ int unknowns(const MapArgs &a, uint64_t i, uint32_t m
     return cnt;
 }
 
-__global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
-                                                      const uint32_t *level, uint32_t *winner) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n_gates) return;
-    const uint32_t m = mask[i];
-    if (!m) return;
-    uint32_t u = 0;
-    int slot = 0;
-    const int cnt = unknowns(a, i, m, level, kUnset, n_vars, u, slot);
-    if (cnt == 0) mask[i] = 0;  // nothing left to define: a plain constraint from here on
-    else if (cnt == 1 && ((m >> (4 + slot)) & 1) && __atomic_load_n(&winner[u], __ATOMIC_RELAXED) > (uint32_t)i)
-        atomicMin(&winner[u], (uint32_t)i);
+// The bids of row i in a round, arithmetic and gate rules alike: put(u, role)
+// for every variable u the row would define, "known" being level < bound.
+// Returns the row's bytes as they are after the round: an arithmetic byte with
+// nothing left to define is cleared, and so is the bit of a gate rule none of
+// whose slots is unknown, or that is ready (whatever it bid for is defined in
+// this round, by this row or by a lower one).
+template <class Put>
+__device__ __forceinline__ void row_bids(const MapArgs &a, uint64_t i, uint32_t &m, uint32_t &gm, const uint32_t *level,
+                                         uint32_t bound, uint64_t n_vars, Put &&put) {
+    auto unknown = [&](uint32_t v) { return v < n_vars && __atomic_load_n(&level[v], __ATOMIC_RELAXED) >= bound; };
+    auto known = [&](uint32_t v) { return v < n_vars && __atomic_load_n(&level[v], __ATOMIC_RELAXED) < bound; };
+    if (m) {
+        uint32_t u = 0;
+        int slot = 0;
+        const int cnt = unknowns(a, i, m, level, bound, n_vars, u, slot);
+        if (cnt == 0) m = 0;  // nothing left to define: a plain constraint from here on
+        else if (cnt == 1 && ((m >> (4 + slot)) & 1)) put(u, (uint32_t)slot);
+    }
+    if (gm & kGateRange) {
+        const bool ready = known(a.var[3][i + 1]);
+        bool left = false;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t v = a.var[j][i];
+            if (!unknown(v)) continue;
+            left = true;
+            if (ready) put(v, (uint32_t)(kSolveRoleRange + j));
+        }
+        if (ready || !left) gm &= ~kGateRange;
+    }
+    if (gm & kGateLogic) {
+        const bool ready = known(a.var[0][i + 1]) && known(a.var[1][i + 1]);
+        bool left = false;
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            const uint32_t v = j < 4 ? a.var[j][i] : a.var[3][i + 1];
+            if (!unknown(v)) continue;
+            left = true;
+            if (ready) put(v, (uint32_t)(kSolveRoleLogic + j));
+        }
+        if (ready || !left) gm &= ~(kGateLogic | kGateXor);
+    }
 }
 
-__global__ __launch_bounds__(256) void k_solve_commit_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
-                                                       uint32_t *level, const uint32_t *winner, uint32_t *def,
-                                                       uint32_t t, uint32_t *count) {
+__global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
+                                                      const uint8_t *gmask, const uint32_t *level, uint32_t *winner) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    bool won = false;
+    if (i >= n_gates) return;
+    uint32_t m = mask[i], gm = gmask ? gmask[i] : 0;
+    if (!m && !gm) return;
+    const uint32_t m0 = m;
+    row_bids(a, i, m, gm, level, kUnset, n_vars, [&](uint32_t u, uint32_t role) {
+        const uint32_t key = 16 * (uint32_t)i + role;
+        if (__atomic_load_n(&winner[u], __ATOMIC_RELAXED) > key) atomicMin(&winner[u], key);
+    });
+    // (a ready gate rule keeps its bit until the commit, which looks at the same rows)
+    if (m0 && !m) mask[i] = 0;
+}
+
+// count[0..3]: the round's definitions by arithmetic, range and logic rules,
+// and those of them that read two values (logic c, d, d_next)
+__global__ __launch_bounds__(256) void k_solve_commit_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
+                                                       uint8_t *gmask, uint32_t *level, const uint32_t *winner,
+                                                       uint32_t *def, uint32_t t, uint32_t *count) {
+    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    uint32_t won[4] = {0, 0, 0, 0};
     if (i < n_gates) {
-        const uint32_t m = mask[i];
-        if (m) {
-            uint32_t u = 0;
-            int slot = 0;
-            const int cnt = unknowns(a, i, m, level, t, n_vars, u, slot);
-            if (cnt == 1 && ((m >> (4 + slot)) & 1) && winner[u] == (uint32_t)i) {
-                won = true;
+        uint32_t m = mask[i], gm = gmask ? gmask[i] : 0;
+        if (m || gm) {
+            const uint32_t gm0 = gm;
+            row_bids(a, i, m, gm, level, t, n_vars, [&](uint32_t u, uint32_t role) {
+                const uint32_t key = 16 * (uint32_t)i + role;
+                if (winner[u] != key) return;
                 __atomic_store_n(&level[u], t, __ATOMIC_RELAXED);
-                def[u] = (uint32_t)(4 * i + slot);
-                mask[i] = 0;
-            }
+                def[u] = key;
+                won[role < kSolveRoleRange ? 0 : role < kSolveRoleLogic ? 1 : 2]++;
+                if (role >= kSolveRoleLogic + 2) won[3]++;
+                if (role < kSolveRoleRange) mask[i] = 0;
+            });
+            if (gm != gm0) gmask[i] = (uint8_t)gm;
         }
     }
-    const unsigned long long b = __ballot(won);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+    // (a lane wins at most ten times: four bits of every counter)
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        if (!gmask && c) break;
+        uint32_t sum = 0;
+#pragma unroll
+        for (int bit = 0; bit < 4; bit++) sum += (uint32_t)__popcll(__ballot((won[c] >> bit) & 1)) << bit;
+        if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&count[c], sum);
+    }
 }
 
 // the variables no round reached: their count and the lowest of them
@@ -175,13 +257,16 @@ __global__ __launch_bounds__(256) void k_solve_unset_(const uint32_t *level, uin
     if ((threadIdx.x & 63) == 0) atomicAdd(&out[0], (uint32_t)__popcll(b));
 }
 
-// sort key: the 0-based level of a solved variable, n_levels for every other
-__global__ __launch_bounds__(256) void k_solve_keys_(const uint32_t *level, uint64_t n_vars, uint32_t n_levels,
-                                                     uint32_t *key) {
+// sort key: the 0-based level of a variable an arithmetic row defines, n_levels
+// + that level for one a gate row defines (only where gate_keys: a plan with
+// gate entries), the key above all of those for every other
+__global__ __launch_bounds__(256) void k_solve_keys_(const uint32_t *level, const uint32_t *def, uint64_t n_vars,
+                                                     uint32_t n_levels, bool gate_keys, uint32_t *key) {
     const uint64_t u = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (u >= n_vars) return;
-    const uint32_t l = level[u];
-    key[u] = l >= 1 && l <= n_levels ? l - 1 : n_levels;
+    const uint32_t l = level[u], rest = gate_keys ? 2 * n_levels : n_levels;
+    if (l < 1 || l > n_levels) key[u] = rest;
+    else key[u] = gate_keys && (def[u] & 15) >= kSolveRoleRange ? n_levels + l - 1 : l - 1;
 }
 
 // entry p: its target, row and wires, and the two denominators coef and coef q_arith
@@ -191,8 +276,8 @@ __global__ __launch_bounds__(256) void k_solve_denoms_(MapArgs a, SolveSel q, co
     const uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (p >= n) return;
     const uint32_t u = order[p] < n_vars ? order[p] : 0, d = def[u];
-    const uint64_t i = d >> 2;
-    const int slot = (int)(d & 3);
+    const uint64_t i = d >> 4;
+    const int slot = (int)(d & 3);  // (an arithmetic role is its slot)
     v.tgt[p] = u;
     v.row[p] = (uint32_t)i;
 #pragma unroll
@@ -254,6 +339,32 @@ __global__ __launch_bounds__(256) void k_solve_out_emit_(MapArgs a, SolveSel q, 
     if (o.coef[kSolveQm]) put(kSolveQm, q.q_m);
 }
 
+// gate entry g: the variable at order[g] and what its (row, role) says it is
+__global__ __launch_bounds__(256) void k_solve_gate_emit_(MapArgs a, SolveSel q, const uint32_t *order,
+                                                          const uint32_t *def, uint64_t n, uint64_t n_gates,
+                                                          uint64_t n_vars, SolveGateView g) {
+    const uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t u = order[p] < n_vars ? order[p] : 0, d = def[u], role = d & 15;
+    const uint64_t i = d >> 4, nx = i + 1 < n_gates ? i + 1 : i;  // (a gate rule's row has a next row)
+    uint32_t sa, sb, kind = kSolveGateShift, shift = 2;
+    if (role < kSolveRoleLogic) {  // range a..d: d_next >> 2, 4, 6, 8
+        sa = sb = a.var[3][nx];
+        shift = 2 * (role - kSolveRoleRange + 1);
+    } else {
+        const uint32_t op = load_fr(q.q_c, i) == Fr::one() ? kSolveGateAnd : kSolveGateXor;
+        sa = a.var[0][nx], sb = a.var[1][nx];
+        switch (role - kSolveRoleLogic) {
+        case 0: sb = sa; break;             // a_i = A >> 2
+        case 1: sa = sb; break;             // b_i = B >> 2
+        case 2: kind = kSolveGateProd, shift = 0; break;
+        case 3: kind = op; break;           // d_i = (A >> 2) op (B >> 2)
+        default: kind = op, shift = 0;      // d_(i+1) = A op B
+        }
+    }
+    g.tgt[p] = u, g.a[p] = sa, g.b[p] = sb, g.word[p] = kind | shift << 8;
+}
+
 __global__ __launch_bounds__(256) void k_solve_scatter_(const uint32_t *ids, const uint64_t *in, uint64_t n_inputs,
                                                         uint64_t *vals) {
     const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -297,6 +408,64 @@ __global__ __launch_bounds__(256) void k_solve_narrow_(SolveView v, uint32_t l0,
     for (uint32_t l = l0; l < l1; l++) {
         const uint64_t p = (uint64_t)v.lvl_off[l] + threadIdx.x;
         if (p < v.lvl_off[l + 1]) solve_entry(v, p, vals, pi);
+        __syncthreads();  // the level's values: written, and visible to this workgroup
+    }
+}
+
+// x >> sh over the eight 32-bit limbs, sh < 32
+__device__ __forceinline__ Fr shr_bits(const Fr &x, uint32_t sh) {
+    Fr r;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint64_t two = (uint64_t)(k < 7 ? x.v[k + 1] : 0u) << 32 | x.v[k];
+        r.v[k] = (uint32_t)(two >> sh);
+    }
+    return r;
+}
+
+// one or two values to canonical form, the quads, and back (SolveGateView)
+__device__ __forceinline__ void solve_gate_entry(const SolveGateView &g, uint64_t p, uint64_t *vals) {
+    const uint32_t w = g.word[p], kind = w & 255, sh = w >> 8;
+    const Fr a = from_mont(load_fr(vals, g.a[p]));
+    Fr r;
+    if (kind == kSolveGateShift) {
+        r = shr_bits(a, sh);
+    } else {
+        const Fr b = from_mont(load_fr(vals, g.b[p]));
+        if (kind == kSolveGateProd) {
+            r = Fr::zero();
+            r.v[0] = (a.v[0] & 3) * (b.v[0] & 3);
+        } else {
+            const Fr x = shr_bits(a, sh), y = shr_bits(b, sh);
+#pragma unroll
+            for (int k = 0; k < 8; k++) r.v[k] = kind == kSolveGateAnd ? x.v[k] & y.v[k] : x.v[k] ^ y.v[k];
+            // an XOR of two integers below r is below 2^255 < 2 r
+            Fr t;
+            if (!sub_n<8>(t.v, r.v, FrP::P)) r = t;
+        }
+    }
+    store_fr(vals, g.tgt[p], to_mont(r));
+}
+
+__global__ __launch_bounds__(256) void k_solve_gate_wide_(SolveGateView g, uint64_t p0, uint64_t p1, uint64_t *vals) {
+    const uint64_t p = p0 + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (p < p1) solve_gate_entry(g, p, vals);
+}
+
+// one workgroup of 512: levels l0 .. l1 - 1, each of at most 256 entries in all;
+// lanes 0..255 (waves 0-3) take the arithmetic entries, lanes 256..511 the gate entries
+__global__ __launch_bounds__(512) void k_solve_mixed_(SolveView v, SolveGateView g, uint32_t l0, uint32_t l1,
+                                                      uint64_t *vals, PiList pi) {
+    const bool gate = threadIdx.x >= 256;
+    const uint32_t lane = threadIdx.x & 255;
+    for (uint32_t l = l0; l < l1; l++) {
+        if (gate) {
+            const uint64_t p = (uint64_t)g.lvl_off[l] + lane;
+            if (p < g.lvl_off[l + 1]) solve_gate_entry(g, p, vals);
+        } else {
+            const uint64_t p = (uint64_t)v.lvl_off[l] + lane;
+            if (p < v.lvl_off[l + 1]) solve_entry(v, p, vals, pi);
+        }
         __syncthreads();  // the level's values: written, and visible to this workgroup
     }
 }
@@ -371,26 +540,34 @@ void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars
 void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
                   const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s) {
     const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
-    DevBuf mask(n_gates), winner(4 * n_vars), ctr(8);
-    uint8_t *d_mask = static_cast<uint8_t *>(mask.p);
+    const bool gates = sel.range || sel.logic;
+    DevBuf mask(n_gates), gmask, winner(4 * n_vars), ctr(16);
+    if (gates) gmask.alloc(n_gates);
+    uint8_t *d_mask = static_cast<uint8_t *>(mask.p), *d_gmask = static_cast<uint8_t *>(gmask.p);
     PNP_HIP(hipMemsetAsync(winner.p, 0xff, 4 * n_vars, s));
     hipLaunchKernelGGL(k_solve_mask_, dim3(nblk(n_gates)), dim3(256), 0, s, sel, n_gates, d_out_bits,
-                       d_mask);
+                       d_mask, d_gmask);
     PNP_HIP(hipGetLastError());
     out.widths.clear();
+    out.gate_widths.clear();
+    out.n_range = out.n_logic = out.n_two = 0;
     // (a round defines at least one variable, so there are at most n_vars of them)
     for (uint64_t t = 1; t <= n_vars; t++) {
-        PNP_HIP(hipMemsetAsync(ctr.p, 0, 4, s));
-        hipLaunchKernelGGL(k_solve_ready_, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_level,
-                           winner.u32());
-        hipLaunchKernelGGL(k_solve_commit_, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_level,
-                           winner.u32(), d_def, (uint32_t)t, ctr.u32());
+        PNP_HIP(hipMemsetAsync(ctr.p, 0, 16, s));
+        hipLaunchKernelGGL(k_solve_ready_, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_gmask,
+                           d_level, winner.u32());
+        hipLaunchKernelGGL(k_solve_commit_, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_gmask,
+                           d_level, winner.u32(), d_def, (uint32_t)t, ctr.u32());
         PNP_HIP(hipGetLastError());
-        uint32_t won = 0;
-        PNP_HIP(hipMemcpyAsync(&won, ctr.p, 4, hipMemcpyDeviceToHost, s));
+        uint32_t won[4] = {0, 0, 0, 0};  // arithmetic, range, logic; of those, two sources
+        PNP_HIP(hipMemcpyAsync(won, ctr.p, 16, hipMemcpyDeviceToHost, s));
         PNP_HIP(hipStreamSynchronize(s));
-        if (!won) break;
-        out.widths.push_back(won);
+        if (!(won[0] + won[1] + won[2])) break;
+        out.widths.push_back(won[0]);
+        out.gate_widths.push_back(won[1] + won[2]);
+        out.n_range += won[1];
+        out.n_logic += won[2];
+        out.n_two += won[3];
     }
     uint32_t un[2] = {0, kUnset};
     PNP_HIP(hipMemcpyAsync(ctr.p, un, 8, hipMemcpyHostToDevice, s));
@@ -402,32 +579,46 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
     out.first_undetermined = un[1];
 }
 
-void solve_emit(const uint32_t *const d_var[4], uint64_t n_vars, const SolveSel &sel, const uint32_t *d_level,
-                const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows, uint64_t n_out,
-                const SolveView &v, hipStream_t s) {
+void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
+                const uint32_t *d_level, const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows,
+                uint64_t n_out, const SolveView &v, const SolveGateView &g, hipStream_t s) {
     const uint32_t n_levels = (uint32_t)b.widths.size();
-    std::vector<uint32_t> off(n_levels + 1, 0);
-    for (uint32_t l = 0; l < n_levels; l++) off[l + 1] = off[l] + b.widths[l];
-    const uint64_t n = off[n_levels];
+    std::vector<uint32_t> off(n_levels + 1, 0), goff(n_levels + 1, 0);
+    for (uint32_t l = 0; l < n_levels; l++) {
+        off[l + 1] = off[l] + b.widths[l];
+        goff[l + 1] = goff[l] + b.gate_widths[l];
+    }
+    const uint64_t n = off[n_levels], n_gate = goff[n_levels];
     PNP_HIP(hipMemcpyAsync(v.lvl_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, s));
+    if (n_gate) PNP_HIP(hipMemcpyAsync(g.lvl_off, goff.data(), 4 * goff.size(), hipMemcpyHostToDevice, s));
     const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
     if (n_out) {  // products, not quotients: no inverse
         hipLaunchKernelGGL(k_solve_out_emit_, dim3(nblk(n_out)), dim3(256), 0, s, a, sel, d_out_rows, n_out, v.out);
         PNP_HIP(hipGetLastError());
     }
-    if (n) {
-        DevBuf keys(4 * n_vars), sort_scratch, den(64 * n), inv_scratch;
-        hipLaunchKernelGGL(k_solve_keys_, dim3(nblk(n_vars)), dim3(256), 0, s, d_level, n_vars, n_levels, keys.u32());
+    if (n + n_gate) {  // the arithmetic entries by level, then (a plan that has them) the gate entries by level
+        DevBuf keys(4 * n_vars), sort_scratch, den, inv_scratch;
+        const uint32_t top = n_gate ? 2 * n_levels : n_levels;
+        hipLaunchKernelGGL(k_solve_keys_, dim3(nblk(n_vars)), dim3(256), 0, s, d_level, d_def, n_vars, n_levels,
+                           n_gate != 0, keys.u32());
         PNP_HIP(hipGetLastError());
         int bits = 1;
-        while (bits < 32 && (n_levels >> bits)) bits++;
+        while (bits < 32 && (top >> bits)) bits++;
         const uint32_t *order = sort_positions_u32(keys.u32(), n_vars, bits, sort_scratch, s);
-        hipLaunchKernelGGL(k_solve_denoms_, dim3(nblk(n)), dim3(256), 0, s, a, sel, order, d_def, n, n_vars, v,
-                           den.u64());
-        PNP_HIP(hipGetLastError());
-        k_batch_inverse(den.u64(), 2 * n, inv_scratch, s);
-        hipLaunchKernelGGL(k_solve_fold_, dim3(nblk(n)), dim3(256), 0, s, sel, n, v, d_def, den.u64());
-        PNP_HIP(hipGetLastError());
+        if (n) {
+            den.alloc(64 * n);
+            hipLaunchKernelGGL(k_solve_denoms_, dim3(nblk(n)), dim3(256), 0, s, a, sel, order, d_def, n, n_vars, v,
+                               den.u64());
+            PNP_HIP(hipGetLastError());
+            k_batch_inverse(den.u64(), 2 * n, inv_scratch, s);
+            hipLaunchKernelGGL(k_solve_fold_, dim3(nblk(n)), dim3(256), 0, s, sel, n, v, d_def, den.u64());
+            PNP_HIP(hipGetLastError());
+        }
+        if (n_gate) {
+            hipLaunchKernelGGL(k_solve_gate_emit_, dim3(nblk(n_gate)), dim3(256), 0, s, a, sel, order + n, d_def,
+                               n_gate, n_gates, n_vars, g);
+            PNP_HIP(hipGetLastError());
+        }
     }
     PNP_HIP(hipStreamSynchronize(s));  // (off and the scratch go out of scope)
 }
@@ -449,6 +640,19 @@ void k_solve_levels(const SolveView &v, uint32_t l0, uint32_t l1, uint64_t p0, u
     const PiList pi{pi_pos, pi_val, n_pi};
     if (wide) hipLaunchKernelGGL(k_solve_wide_, dim3(nblk(p1 - p0)), dim3(256), 0, s, v, p0, p1, d_vals, pi);
     else hipLaunchKernelGGL(k_solve_narrow_, dim3(1), dim3(256), 0, s, v, l0, l1, d_vals, pi);
+    PNP_HIP(hipGetLastError());
+}
+
+void k_solve_gate_level(const SolveGateView &g, uint64_t g0, uint64_t g1, uint64_t *d_vals, hipStream_t s) {
+    if (g1 <= g0) return;
+    hipLaunchKernelGGL(k_solve_gate_wide_, dim3(nblk(g1 - g0)), dim3(256), 0, s, g, g0, g1, d_vals);
+    PNP_HIP(hipGetLastError());
+}
+
+void k_solve_mixed_levels(const SolveView &v, const SolveGateView &g, uint32_t l0, uint32_t l1, uint64_t *d_vals,
+                          const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s) {
+    const PiList pi{pi_pos, pi_val, n_pi};
+    hipLaunchKernelGGL(k_solve_mixed_, dim3(1), dim3(512), 0, s, v, g, l0, l1, d_vals, pi);
     PNP_HIP(hipGetLastError());
 }
 

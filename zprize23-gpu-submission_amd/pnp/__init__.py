@@ -42,6 +42,7 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_check_assignment", "pnp_check_witness",
            "pnp_load_solve_inputs", "pnp_solve_assignment", "pnp_assignment_ptr", "pnp_assignment_values",
            "pnp_load_solve_plan", "pnp_solved_public_inputs", "pnp_prove_solved", "pnp_check_solved",
+           "pnp_load_solve_plan_gates", "pnp_solve_gate_entries",
            "pnp_lde_blocks", "pnp_to_blocks", "pnp_intt_blocks", "pnp_t_combine_blocks", "pnp_t_combine_range")
 
 
@@ -332,6 +333,26 @@ class Context:
         if rc != -1:
             check(rc, "pnp_load_solve_plan")
         return rc, info
+
+    def load_solve_plan_gates(self, ids: int, n_inputs: int, rows: int, n_outputs: int, gates: int,
+                              device_ptrs: bool = False):
+        """pnp_load_solve_plan_gates: load_solve_plan where the rows of the
+        families in `gates` (abi.SOLVE_RANGE | abi.SOLVE_LOGIC) define their
+        quads from the next row's accumulators.  Returns (rc, abi.SolveInfo)
+        as load_solve_inputs."""
+        info = abi.SolveInfo()
+        rc = self.lib.pnp_load_solve_plan_gates(self.h, C.c_void_p(ids or None), n_inputs, C.c_void_p(rows or None),
+                                                n_outputs, gates, int(device_ptrs), C.byref(info))
+        if rc != -1:
+            check(rc, "pnp_load_solve_plan_gates")
+        return rc, info
+
+    def solve_gate_entries(self):
+        """pnp_solve_gate_entries: (entries range rows define, entries logic
+        rows define) of the resident plan."""
+        out = (C.c_uint64 * 2)()
+        check(self.lib.pnp_solve_gate_entries(self.h, C.byref(out)), "pnp_solve_gate_entries")
+        return out[0], out[1]
 
     def solved_public_inputs(self):
         """pnp_solved_public_inputs: [(row, canonical value int)] of the last

@@ -174,7 +174,14 @@ class SolveInfo(C.Structure):
 #   pnp_solved_public_inputs(ctx, pos, canon, cap, &n)
 #   pnp_prove_solved(ctx, n_pi, pi_pos, pi_canon, label, out)
 #   pnp_check_solved(ctx, n_pi, pi_pos, pi_canon, report)
+# With range and logic rows that define (gates: SOLVE_RANGE | SOLVE_LOGIC):
+#   pnp_load_solve_plan_gates(ctx, input_ids, n_inputs, output_rows, n_outputs, gates, device_ptrs, info)
+#   pnp_solve_gate_entries(ctx, out[2])
+SOLVE_RANGE, SOLVE_LOGIC = 1, 2
 SOLVE_ARGTYPES = {
+    "pnp_load_solve_plan_gates": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,
+                                  C.POINTER(SolveInfo)],
+    "pnp_solve_gate_entries": [C.c_void_p, C.POINTER(C.c_uint64 * 2)],
     "pnp_load_solve_plan": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
                             C.POINTER(SolveInfo)],
     "pnp_solved_public_inputs": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
