@@ -1,5 +1,5 @@
 """The satisfiability check on the MI355X: pnp_check_assignment and
-pnp_check_witness (csrc/check.hip, csrc/abi.cpp) against the plain-integer
+pnp_check_witness (csrc/check.hip, csrc/check_witness.cpp) against the plain-integer
 model of tests/test_check_ref.py.  A satisfied witness gives PNP_OK and a zero
 report; a violated one PNP_E_UNSAT and a report equal to the model's in every
 field (counts by kind, the first (row, kind, index)), whatever order the

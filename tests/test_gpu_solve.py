@@ -1,5 +1,5 @@
 """The witness solver on the MI355X: pnp_load_solve_inputs (the plan, built on
-the device) and pnp_solve_assignment (csrc/solve.hip, csrc/abi.cpp) against the
+the device) and pnp_solve_assignment (csrc/solve.hip, csrc/solve_witness.cpp) against the
 plain-integer model of tests/solve_ref.py.  Every comparison is exact: field
 elements, counts, proof bytes.
 

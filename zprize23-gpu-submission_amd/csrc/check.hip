@@ -5,7 +5,7 @@
 // and nothing says where.  Here the same constraint expressions (widgets.cuh
 // c_range / c_logic / c_fbsm / c_cadd, whose values w_* sum up) run on the
 // D rows of the domain itself, one at a time, over the selector ROW values
-// (forward transforms of the resident coefficients, abi.cpp check_columns):
+// (forward transforms of the resident coefficients, check_witness.cpp):
 // the composer's check_circuit_satisfied on the GPU.
 //
 //   k_check_arith_      a lane a row: the arithmetic gate + the row's public

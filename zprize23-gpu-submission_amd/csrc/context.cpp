@@ -592,6 +592,39 @@ void commit_affine_batch(pnp_ctx *ctx, const uint64_t *const *d_scalars, int B, 
     store_affine(xyzz.data(), B, out);
 }
 
+// ---- shared by the check and the solver (check_witness.cpp, solve_witness.cpp)
+const uint64_t *KeyRowValues::values(KeyPoly r) {
+    if (!ctx->key.has(r)) return nullptr;
+    const uint64_t *const *coeffs = reinterpret_cast<const uint64_t *const *>(&ctx->key.dev);
+    rows[r].alloc(32ULL << lg);
+    ntt_run(ctx->ntt, rows[r].u64(), lg, false, false, ctx->stream, coeffs[kKeyTable[r].coeffs]);
+    return rows[r].u64();
+}
+
+void DevicePis::upload(const std::vector<uint64_t> &pi_pos, const std::vector<Fr> &pi_val, hipStream_t s) {
+    n = (uint32_t)pi_pos.size();
+    if (!n) return;
+    // (the values start 16-byte aligned: an even count of words before them)
+    const size_t val_off = (pi_pos.size() + 1) & ~size_t(1);
+    std::vector<uint64_t> packed(val_off + 4 * pi_pos.size());
+    for (size_t k = 0; k < pi_pos.size(); k++) {
+        packed[k] = pi_pos[k];
+        to_u64_limbs(pi_val[k], &packed[val_off + 4 * k]);
+    }
+    buf.alloc(8 * packed.size());
+    PNP_HIP(hipMemcpyAsync(buf.p, packed.data(), 8 * packed.size(), hipMemcpyHostToDevice, s));
+    PNP_HIP(hipStreamSynchronize(s));
+    pos = buf.u64();
+    val = buf.u64() + val_off;
+}
+
+void refuse_sharded(pnp_ctx *ctx, const char *what, const char *noun) {
+    if (ctx->msm.world <= 1) return;
+    set_error("%s: the context is sharded over %d ranks (a multi-rank %s is not supported)", what, ctx->msm.world,
+              noun);
+    throw Error(PNP_E_ARG);
+}
+
 }  // namespace pnp
 
 hipStream_t pnp_ctx::side_stream() {

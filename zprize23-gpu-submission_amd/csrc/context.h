@@ -6,6 +6,7 @@
 #include "prover_key.h"
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <memory>
 #include <thread>
 
@@ -141,8 +142,7 @@ struct H2D {
 void h2d_batch(pnp_ctx *ctx, const std::vector<H2D> &copies);
 // device bytes held by every DevBuf of the process, now and at most (pnp_hbm_usage)
 extern std::atomic<uint64_t> g_dev_live, g_dev_peak;
-// shared by context.cpp and abi.cpp only: kept out of the library's exports
-#define PNP_HIDDEN __attribute__((visibility("hidden")))
+// (PNP_HIDDEN, pnp_internal.h: shared between the library's units only)
 // free the staging pool (pnp_ctx_destroy)
 PNP_HIDDEN void h2d_release(pnp_ctx *ctx);
 // this thread's last error message (set_error writes it, pnp_last_error returns it)
@@ -206,7 +206,7 @@ struct Assignment {
     const uint64_t *values;
     uint64_t n_vars;
 };
-// What a proof and a satisfiability check (abi.cpp pnp_check_*) decide alike
+// What a proof and a satisfiability check (check_witness.cpp) decide alike
 // before any work (prover.cpp).  prove_domain: the keys are loaded (the commit
 // key only with need_ck), an assignment has its wire map and variable count,
 // and the domain n = 2^lg of the inputs is the resident key's; ng = the gate
@@ -223,6 +223,78 @@ void public_input_map(const ProveOpts &opt, uint64_t n, std::vector<uint64_t> &p
 // key's, the gates and q_lookup rows the resident wire map's.  Throws Error.
 void prove_impl(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, ProofC *out, const ProveOpts *opt = nullptr,
                 const Assignment *asg = nullptr);
+
+// ---- what the proof, the check and the solver share (context.cpp) ----
+// the argument tests of their entry points (each keeps its own message)
+static inline bool pis_given(uint64_t n_pi, const uint64_t *pos, const uint64_t *canon) {
+    return !n_pi || (pos && canon);
+}
+static inline bool hbm_aligned(const void *p) { return ((uintptr_t)p & 15) == 0; }  // Fr move 16 bytes at a time
+// the stage clock of a call (pnp_last_stage_times): a stage ends when the context's stream has drained
+struct PNP_HIDDEN StageTimer {
+    pnp_ctx *ctx;
+    std::chrono::steady_clock::time_point t0;
+    explicit StageTimer(pnp_ctx *c) : ctx(c) {}
+    void start() {
+        ctx->stages.clear();
+        t0 = std::chrono::steady_clock::now();
+    }
+    void mark(const char *name) {
+        PNP_HIP(hipStreamSynchronize(ctx->stream));
+        const auto t1 = std::chrono::steady_clock::now();
+        ctx->stages.emplace_back(name, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    }
+};
+// The row values of the key's polynomials on the domain 2^lg: a forward
+// transform of the resident coefficients into a buffer of its own, when it is
+// asked for; nullptr for an optional selector the key does not have
+struct PNP_HIDDEN KeyRowValues {
+    pnp_ctx *ctx;
+    uint32_t lg;
+    DevBuf rows[kKeyRows];
+    const uint64_t *values(KeyPoly r);
+};
+// The public inputs of public_input_map in HBM: ascending rows, then their
+// Montgomery values 16-byte aligned; one copy and a sync, nothing when there are none
+struct PNP_HIDDEN DevicePis {
+    DevBuf buf;
+    const uint64_t *pos = nullptr, *val = nullptr;
+    uint32_t n = 0;
+    void upload(const std::vector<uint64_t> &pi_pos, const std::vector<Fr> &pi_val, hipStream_t s);
+};
+// the check and the solver run on one GPU: "<what>: the context is sharded ... (a multi-rank <noun> ...)"
+PNP_HIDDEN void refuse_sharded(pnp_ctx *ctx, const char *what, const char *noun);
+// the caller's four columns into dst (n rows each, zero from row ng on) on the
+// context's stream: device copies now, host columns added to `up` for one
+// h2d_batch with whatever else the caller stages (prover.cpp)
+PNP_HIDDEN void stage_wire_columns(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t *const dst[4],
+                                   uint64_t ng, uint64_t n, std::vector<H2D> &up);
+
+// ---- the satisfiability check (check_witness.cpp); pis: n_pi, pi_pos, pi_canon ----
+PNP_HIDDEN void check_assignment(pnp_ctx *ctx, const Assignment &asg, int device_ptrs, const ProveOpts &pis,
+                                 pnp_check_report *report);
+PNP_HIDDEN void check_witness(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, const ProveOpts &pis,
+                              pnp_check_report *report);
+// ---- the witness solver (solve_witness.cpp); `what` opens the messages of a plan build ----
+PNP_HIDDEN void load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, uint64_t n_inputs,
+                                const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, int device_ptrs,
+                                pnp_solve_info *info);
+PNP_HIDDEN void solve_gate_entries(pnp_ctx *ctx, uint64_t out[2]);
+PNP_HIDDEN void solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs,
+                                 const ProveOpts &pis);
+PNP_HIDDEN void assignment_ptr(pnp_ctx *ctx, uint64_t **d_values, uint64_t *n_vars);
+PNP_HIDDEN void assignment_values(pnp_ctx *ctx, const uint32_t *ids, uint64_t k, uint64_t *out);
+PNP_HIDDEN void solved_public_inputs(pnp_ctx *ctx, uint64_t *pos, uint64_t *canon, uint64_t cap, uint64_t *n);
+// The resident solution as pnp_prove_solved / pnp_check_solved pass it on: the
+// caller's public inputs (none on an output row) and then the derived ones; returns the code
+struct PNP_HIDDEN SolvedAssignment {
+    std::vector<uint64_t> pos, canon;
+    uint64_t *values = nullptr;
+    uint64_t n_vars = 0;
+};
+PNP_HIDDEN int solved_assignment(pnp_ctx *ctx, const char *what, uint64_t n_pi, const uint64_t *pi_pos,
+                                 const uint64_t *pi_canon, SolvedAssignment &out);
 }  // namespace pnp
 
 // the body of a v2 entry point: codes, never exceptions (bad_alloc,

@@ -13,6 +13,8 @@
 namespace pnp {
 
 void set_error(const char *fmt, ...);
+// shared between the library's units only: kept out of its exports
+#define PNP_HIDDEN __attribute__((visibility("hidden")))
 
 #define PNP_HIP(expr)                                                              \
     do {                                                                           \

@@ -25,7 +25,6 @@
 //   * the 14 commitments in the openings whose values never reach the proof
 //     (gen_proof.cuh:421, 450: aw/saw commits only feed empty randomness) are
 //     not computed; z_comm is the z commitment (saw_commits[0] == commit(z)).
-#include <chrono>
 #include <string.h>
 #include "context.h"
 #include "protocol.h"
@@ -50,22 +49,6 @@ Fr root_of_unity(uint32_t lg) {
 }
 
 namespace {
-
-struct Timer {
-    pnp_ctx *ctx;
-    std::chrono::steady_clock::time_point t0;
-    explicit Timer(pnp_ctx *c) : ctx(c) {}
-    void start() {
-        ctx->stages.clear();
-        t0 = std::chrono::steady_clock::now();
-    }
-    void mark(const char *name) {
-        PNP_HIP(hipStreamSynchronize(ctx->stream));
-        auto t1 = std::chrono::steady_clock::now();
-        ctx->stages.emplace_back(name, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
 
 void append_comm(Transcript &t, const char *label, const CommitmentC &c) {
     t.append_point(label, c.x, c.y);
@@ -164,6 +147,17 @@ void public_input_map(const ProveOpts &opt, uint64_t n, std::vector<uint64_t> &p
     }
 }
 
+// the caller's columns, padded (context.h): Proof::load_witness and the check stage them alike
+void stage_wire_columns(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs, uint64_t *const dst[4], uint64_t ng,
+                        uint64_t n, std::vector<H2D> &up) {
+    const uint64_t *wsrc[4] = {cs->w_l, cs->w_r, cs->w_o, cs->w_4};
+    for (int j = 0; j < 4; j++) {
+        if (device_ptrs) PNP_HIP(hipMemcpyAsync(dst[j], wsrc[j], 32 * ng, hipMemcpyDeviceToDevice, ctx->stream));
+        else up.push_back({dst[j], wsrc[j], 32 * ng});
+        if (n > ng) PNP_HIP(hipMemsetAsync(dst[j] + 4 * ng, 0, 32 * (n - ng), ctx->stream));
+    }
+}
+
 namespace {
 
 // Round 5's evaluations (Montgomery).  kEvalTable below is their one list:
@@ -240,7 +234,7 @@ struct Proof {
     std::vector<uint64_t> pi_pos;
     std::vector<Fr> pi_val;
     Transcript tr;
-    Timer tm;
+    StageTimer tm;
     // ---- the witness (load_witness): padded columns; qlk: the q_lookup rows,
     // the first qlk_rows of them read (none: a zero column)
     uint64_t *wsc[4] = {}, *wpoly[4] = {};  // wire columns, wire coefficients (round 1)
@@ -417,8 +411,8 @@ void Proof::load_witness() {
             inputs_h2d = 32.0 * asg->n_vars;
             vals = dv;
         }
-        const uint32_t *var = static_cast<const uint32_t *>(ctx->key.wm_var.p);
-        const uint32_t *dvar[4] = {var, var + ng, var + 2 * ng, var + 3 * ng};
+        const uint32_t *dvar[4];
+        ctx->key.wm_columns(dvar);
         hipEvent_t e0 = nullptr;
         ctx->ktimer.begin("gather_witness", s, e0);
         k_gather_witness(dvar, ng, vals, asg->n_vars, lg, wsc, s);
@@ -427,13 +421,8 @@ void Proof::load_witness() {
         else qlk_rows = 0;
         alg(4.0 * (ng / 8.0 + ng + n));  // ids, gathered values, padded columns
     } else {
-        const uint64_t *wsrc[4] = {cs->w_l, cs->w_r, cs->w_o, cs->w_4};
         std::vector<H2D> up;  // a host witness: staged uploads (context.cpp h2d_batch)
-        for (int j = 0; j < 4; j++) {
-            if (device_ptrs) PNP_HIP(hipMemcpyAsync(wsc[j], wsrc[j], 32 * ng, hipMemcpyDeviceToDevice, s));
-            else up.push_back({wsc[j], wsrc[j], 32 * ng});
-            if (n > ng) PNP_HIP(hipMemsetAsync(wsc[j] + 4 * ng, 0, 32 * (n - ng), s));
-        }
+        stage_wire_columns(ctx, cs, device_ptrs, wsc, ng, n, up);
         uint64_t *q = ctx->buf("qlk", n);
         if (device_ptrs) PNP_HIP(hipMemcpyAsync(q, cs->q_lookup, 32 * ng, hipMemcpyDeviceToDevice, s));
         else up.push_back({q, cs->q_lookup, 32 * ng});

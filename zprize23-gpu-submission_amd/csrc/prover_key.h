@@ -185,6 +185,9 @@ struct ResidentKey {
     // the row values of q_lookup on the domain (n Fr), from the resident
     // coefficients when the map became resident; empty: the zero polynomial
     DevBuf wm_qlk;
+    void wm_columns(const uint32_t *d[4]) const {
+        for (int j = 0; j < 4; j++) d[j] = wm_var.u32() + j * wm_gates;
+    }
     void wire_map_drop() {
         wm_loaded = false;
         wm_gates = wm_vars = 0;
@@ -222,6 +225,27 @@ struct ResidentKey {
             bool wide;
         };
         std::vector<Run> runs;
+        // from the levels' widths (arithmetic and gate entries): a level wider
+        // than a workgroup, both segments counted, alone; narrower ones in runs
+        PNP_HIDDEN static std::vector<Run> launch_runs(const std::vector<uint32_t> &widths,
+                                                       const std::vector<uint32_t> &gate_widths) {
+            std::vector<Run> runs;
+            uint64_t p = 0, g = 0;
+            for (uint32_t l = 0; l < widths.size(); l++) {
+                const uint64_t wa = widths[l], wg = gate_widths[l];
+                const bool wide = wa + wg > 256;
+                if (!wide && !runs.empty() && !runs.back().wide) {
+                    runs.back().l1 = l + 1;
+                    runs.back().p1 = p + wa;
+                    runs.back().g1 = g + wg;
+                } else {
+                    runs.push_back({l, l + 1, p, p + wa, g, g + wg, wide});
+                }
+                p += wa;
+                g += wg;
+            }
+            return runs;
+        }
         DevBuf solution;  // n_vars Fr of the last solve; empty before it
         void drop() {
             loaded = false;

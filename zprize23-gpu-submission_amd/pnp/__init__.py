@@ -217,12 +217,7 @@ class Context:
 
     def prove_ex(self, cs: abi.CircuitC, device_ptrs: bool, pis, label: bytes = b"Merkle tree"):
         """pnp_prove_ex: pis = [(position, canonical value int)], any order."""
-        k = len(pis)
-        pos = (C.c_uint64 * max(k, 1))(*[p for p, _ in pis])
-        vals = (C.c_uint64 * max(4 * k, 1))()
-        for i, (_, v) in enumerate(pis):
-            for j in range(4):
-                vals[4 * i + j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+        k, pos, vals = self._pi_args(pis)
         out = abi.ProofC()
         check(self.lib.pnp_prove_ex(self.h, C.byref(cs), int(device_ptrs), k, pos, vals, label,
                                     C.byref(out)), "pnp_prove_ex")
@@ -238,12 +233,7 @@ class Context:
                          label: bytes = b"Merkle tree") -> abi.ProofC:
         """pnp_prove_assignment: values = address (host, or HBM with
         device_ptrs) of n_vars Montgomery Fr by variable id; pis as prove_ex."""
-        k = len(pis)
-        pos = (C.c_uint64 * max(k, 1))(*[p for p, _ in pis])
-        vals = (C.c_uint64 * max(4 * k, 1))()
-        for i, (_, v) in enumerate(pis):
-            for j in range(4):
-                vals[4 * i + j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+        k, pos, vals = self._pi_args(pis)
         out = abi.ProofC()
         check(self.lib.pnp_prove_assignment(self.h, C.c_void_p(values), n_vars, int(device_ptrs), k,
                                             C.cast(pos, C.c_void_p), C.cast(vals, C.c_void_p), label,
@@ -290,11 +280,13 @@ class Context:
         of n_inputs u32 variable ids.  Returns (rc, abi.SolveInfo); raises on
         every error but PNP_E_ARG, whose info says what stayed undetermined
         (last_error() names the id)."""
+        return self._load_solve("pnp_load_solve_inputs", C.c_void_p(ids or None), n_inputs, int(device_ptrs))
+
+    def _load_solve(self, name: str, *args):
         info = abi.SolveInfo()
-        rc = self.lib.pnp_load_solve_inputs(self.h, C.c_void_p(ids or None), n_inputs, int(device_ptrs),
-                                            C.byref(info))
+        rc = getattr(self.lib, name)(self.h, *args, C.byref(info))
         if rc != -1:
-            check(rc, "pnp_load_solve_inputs")
+            check(rc, name)
         return rc, info
 
     def solve_assignment(self, inputs: int, n_inputs: int, device_ptrs: bool, pis=()):
@@ -327,12 +319,8 @@ class Context:
         """pnp_load_solve_plan: load_solve_inputs with output rows; rows =
         address (host, or HBM with device_ptrs, as ids) of n_outputs u64 row
         indices.  Returns (rc, abi.SolveInfo) as load_solve_inputs."""
-        info = abi.SolveInfo()
-        rc = self.lib.pnp_load_solve_plan(self.h, C.c_void_p(ids or None), n_inputs, C.c_void_p(rows or None),
-                                          n_outputs, int(device_ptrs), C.byref(info))
-        if rc != -1:
-            check(rc, "pnp_load_solve_plan")
-        return rc, info
+        return self._load_solve("pnp_load_solve_plan", C.c_void_p(ids or None), n_inputs, C.c_void_p(rows or None),
+                                n_outputs, int(device_ptrs))
 
     def load_solve_plan_gates(self, ids: int, n_inputs: int, rows: int, n_outputs: int, gates: int,
                               device_ptrs: bool = False):
@@ -340,12 +328,8 @@ class Context:
         families in `gates` (abi.SOLVE_RANGE | abi.SOLVE_LOGIC) define their
         quads from the next row's accumulators.  Returns (rc, abi.SolveInfo)
         as load_solve_inputs."""
-        info = abi.SolveInfo()
-        rc = self.lib.pnp_load_solve_plan_gates(self.h, C.c_void_p(ids or None), n_inputs, C.c_void_p(rows or None),
-                                                n_outputs, gates, int(device_ptrs), C.byref(info))
-        if rc != -1:
-            check(rc, "pnp_load_solve_plan_gates")
-        return rc, info
+        return self._load_solve("pnp_load_solve_plan_gates", C.c_void_p(ids or None), n_inputs,
+                                C.c_void_p(rows or None), n_outputs, gates, int(device_ptrs))
 
     def solve_gate_entries(self):
         """pnp_solve_gate_entries: (entries range rows define, entries logic
