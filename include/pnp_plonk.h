@@ -670,8 +670,8 @@ int pnp_check_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const 
  *     i + 1).  This extends "the lowest row defines it" and keeps the plan the
  *     same on every run.  Arithmetic rows behave as above, output rows never
  *     bid, and a variable that nothing reaches is undetermined as above.
- * Fixed-base and curve-addition rows (they would invert, and can fail) and
- * lookup rows (a table search) still never define anything.
+ * Lookup rows (a table search) still never define anything; fixed-base and
+ * curve-addition rows define through pnp_load_solve_plan_ecc, below.
  * A gate entry is 16 bytes (target, two sources, kind and shift) in arrays of
  * their own beside the arithmetic entries, level order, by variable id within
  * a level, with their own level offsets, all counted in plan_bytes; with
@@ -690,6 +690,84 @@ int pnp_load_solve_plan_gates(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t 
                               const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates,
                               int device_ptrs, pnp_solve_info *info /* may be NULL */);
 int pnp_solve_gate_entries(pnp_ctx *ctx, uint64_t out[2]);
+
+/* Fixed-base and curve-addition rows that define: points from scalars.  The
+ * reference's fixed_base_scalar_mul ends with assert_equal(last accumulated
+ * bit, scalar) and point_addition_gate puts its result in the next row, so a
+ * circuit that derives a key or opens a commitment needs no accumulator from
+ * the host: the scalar chain unrolls upwards one row a round, then the point
+ * chain downwards (about 2 + 254 + 255 levels for one 255-row multiplication,
+ * shared by every multiplication of the circuit).
+ *
+ * pnp_load_solve_plan_ecc is pnp_load_solve_plan_gates with `ecc`, the ECC
+ * families whose rows may define (PNP_SOLVE_FIXED_ADD | PNP_SOLVE_VAR_ADD);
+ * pnp_load_solve_plan_gates is this call with ecc = 0: the same plan, info,
+ * plan_bytes, errors, launches and solution.  An ecc bit outside the two flags
+ * is PNP_E_ARG (the message names ecc); gates is validated as above; a flag
+ * for a family whose selector the key does not have is accepted.
+ * The rules join the ones above, in the same rounds; in round t every rule
+ * looks at K_(t-1).  A row i of either family takes part only when
+ * i + 1 < n_gates and i is not an output row.  "Canonical" is the integer
+ * 0 <= V < r; A and D are Jubjub's a = -1 and d.
+ *   FIXED_ADD (flag set, fixed_group_add_selector[i] != 0).  Slots: a, b the
+ *     point accumulator, c is xy_alpha, d the scalar accumulator; q_l, q_r, q_c
+ *     are x_beta, y_beta, xy_beta.  Three independent sub-rules:
+ *     scalar: READY when the variable in slot d of row i + 1 is known; bids for
+ *       slot d of row i.  With V the canonical d_next, d = (V - s) / 2 on
+ *       integers, s = 0 for V even, 1 for V = 1 (mod 4), -1 for V = 3 (mod 4):
+ *       the lowest digit of the width-2 NAF the reference's find_wnaf(2)
+ *       produces, so unrolled upwards from assert_equal(last accumulated bit,
+ *       scalar) it reproduces the reference's scalar_acc exactly.  V + 1 <= r:
+ *       no reduction.
+ *     xy: READY when slots d of rows i and i + 1 are known; bids for slot c of
+ *       row i: c = bit q_c, with bit = d_next - 2 d in the field.
+ *     point: READY when slots a, b, d of row i and slot d of row i + 1 are
+ *       known; bids for slots a and b of row i + 1.  With x_alpha = q_l bit,
+ *       y_alpha = bit^2 (q_r - 1) + 1 and m = (bit q_c) a b D:
+ *         a_next = (x_alpha b + y_alpha a) / (1 + m),
+ *         b_next = (y_alpha b - A x_alpha a) / (1 - m).
+ *       Slot c is not read: its value is what the xy sub-rule would write, so
+ *       the point chain does not wait a round for it.
+ *   VAR_ADD (flag set, variable_group_add_selector[i] != 0): READY when slots
+ *     a, b, c, d of row i are all known; bids for slots d, a, b of row i + 1.
+ *     d_next = a d; with t = D d_next (b c):
+ *       a_next = (d_next + b c) / (1 + t),  b_next = (b d - A a c) / (1 - t).
+ *   Both: a division by zero yields 0 (the device inverse has inv(0) = 0), so
+ *     the solve still cannot fail; the row's own constraint then fails in
+ *     pnp_check_*, as it must.  A slot whose variable is already known is not
+ *     redefined (the composer's constants, inputs, the zero variable): it
+ *     stays a plain constraint for pnp_check_*.
+ *   TIES: the least (row, role) still wins, the row the row whose rule fires;
+ *     the role order goes on after logic's d_next: fixed-add d, c, a_next,
+ *     b_next, then var-add a_next, b_next, d_next.  The order of every bid of
+ *     the rules above is unchanged, so their plans are too.
+ * A scalar whose width-2 NAF has more digits than the multiplication has rows
+ * (the reference's composer asserts on it) is solved all the same; the first
+ * fixed-add row's constraint 0 then fails in pnp_check_*.
+ * The plan: a fixed-add scalar definition is one more kind of the 16-byte gate
+ * entry, (A - s) / 2 (its variables count in pnp_solve_ecc_entries, not in
+ * pnp_solve_gate_entries).  The xy, point and var-add definitions are ECC
+ * entries in arrays of their own, level order, by (row, kind) within a level,
+ * with their own level offsets: 128 bytes an entry, read 16 bytes at a time:
+ * three targets (~0: not won) and the kind, four sources, and the row's q_l,
+ * q_r, q_c (Montgomery; the selector rows are released after the build).  A
+ * point or var-add entry inverts once, (1 + m)(1 - m), for both quotients.
+ * All of it is counted in plan_bytes; with ecc = 0, or no such row defining
+ * anything, nothing is allocated.  A level is an arithmetic, a gate and an ECC
+ * segment: more than 256 entries in all, a launch a segment; narrower levels
+ * with ECC entries share one workgroup in which the ECC entries have waves of
+ * their own.
+ * pnp_solve_info counts every defined variable of every kind in n_solved and
+ * max_width.  pnp_solve_gate_entries keeps counting range and logic only;
+ * pnp_solve_ecc_entries: out[0], out[1] = the variables fixed-add rows, var-add
+ * rows define in the resident plan (PNP_E_NOKEY without a plan).  Everything
+ * that takes a plan takes this one the same way, as listed above; the stage
+ * list is unchanged and solve_levels times every kind of entry. */
+enum { PNP_SOLVE_FIXED_ADD = 1, PNP_SOLVE_VAR_ADD = 2 };
+int pnp_load_solve_plan_ecc(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs,
+                            const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates,
+                            uint32_t ecc, int device_ptrs, pnp_solve_info *info /* may be NULL */);
+int pnp_solve_ecc_entries(pnp_ctx *ctx, uint64_t out[2]);
 
 /* Per-stage wall-clock (ms) of the last pnp_prove, for the bench/profiles.
  * Writes up to `cap` doubles and their names; returns the stage count. */

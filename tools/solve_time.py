@@ -45,7 +45,25 @@ the composer and tiled with numpy; the tiling is asserted to reproduce a
 three-unit composer circuit exactly.  The inputs are the p and q alone.
 Measured: the plan build (three times), the solve (--reps), the solve_levels
 kernels' own time, the entries by family and plan_bytes.  The solution must
-pass pnp_check_solved and hold the sums and the XORs Python computes."""
+pass pnp_check_solved and hold the sums and the XORs Python computes.
+
+    timeout -k 10 900 python tools/solve_time.py --ecc [--inverse binary] [--out profiles/solve_ecc_time.json]
+
+Fixed-base and curve-addition rows that define (pnp_load_solve_plan_ecc): K
+units of a sum s = p + q, the reference's 255-row fixed_base_scalar_mul of s
+and a point_addition_gate that adds the result to a running point
+(tests/ecc_circuits.py), for K = 1 and K = 1024 on D = 2^19: the depth (about
+2 + 254 + 255 levels a multiplication, then one a var-add row) is paid once
+whatever K.  One unit is built by the composer and tiled with numpy, the
+running point's variables patched to the unit before; the tiling is asserted to
+reproduce a three-unit composer circuit.  The inputs are the first point and
+the p and q alone.  Measured per K: the plan build (three times), the solve
+(--reps), the solve_levels kernels' own time, levels and entries by family.
+The solution must pass pnp_check_solved, and the first unit's sum must be
+Python's.  --inverse names the inversion the loaded library was built with
+(csrc/solve.hip kEccInverseBinary: "binary", or "fermat" for a library built
+with -DPNP_ECC_INVERSE_BINARY=0 and given in PNP_PLONK_LIB); the result goes
+under that name, beside what the file already holds."""
 import argparse
 import json
 import os
@@ -467,6 +485,145 @@ def main_gates(args, reps):
     print(json.dumps(out))
 
 
+ECC_SELECTORS = SELECTORS + ("fixed_group_add_selector", "variable_group_add_selector")
+
+
+def ecc_circuit(units, tpl=None):
+    """(var (4, n_gates) u32, {selector: rows}, n_vars, input ids, the last sum's (x, y) ids, the first unit's
+    sum ids): from the composer itself (tpl None), or the one-unit template tiled.  Variables 1, 2 are the
+    first running point."""
+    from circuits import Composer, jj_point
+    from ecc_circuits import fixed_base_mul_of, point_add_of
+    from gate_circuits import M1
+    from test_preprocess_ref import wire_map
+    if tpl is None:
+        cp = Composer(1)
+        rng = np.random.default_rng(1)
+        base = jj_point(cp.rng)
+        start = jj_point(cp.rng)
+        run = (cp.var(start[0]), cp.var(start[1]))
+        ids, sums = [0, *run], []
+        for _ in range(units):
+            p, q = cp.var(int(rng.integers(0, 1 << 62))), cp.var(int(rng.integers(0, 1 << 62)))
+            sv = cp.var(cp.vals[p] + cp.vals[q])
+            cp.row({"q_arith": 1, "q_l": 1, "q_r": 1, "q_o": M1}, p, q, sv, 0)
+            _, res = fixed_base_mul_of(cp, sv, base)
+            _, run = point_add_of(cp, run, res)
+            ids += [p, q]
+            sums.append(run)
+        cols = {name: mont_rows([r[0].get(name, 0) for r in cp.rows]) for name in ECC_SELECTORS}
+        assert not any(k not in ECC_SELECTORS for r in cp.rows for k in r[0])
+        return wire_map(cp), cols, len(cp.vals), ids, sums[-1], sums[0], (base, start)
+    var1, cols1, n_vars1, ids1, last1, _, pts = tpl
+    per, rows = n_vars1 - 3, var1.shape[1]
+    tiled = np.tile(var1.astype(np.int64), (1, units))
+    unit = np.repeat(np.arange(units, dtype=np.int64), rows)[None, :]
+    var = np.where(tiled >= 3, tiled + per * unit, tiled)
+    for j, prev in ((1, last1[0]), (2, last1[1])):  # the running point: the unit before's sum
+        var = np.where((tiled == j) & (unit > 0), prev + per * (unit - 1), var)
+    cols = {name: np.ascontiguousarray(np.tile(c, (units, 1))) for name, c in cols1.items()}
+    off = per * np.arange(units, dtype=np.int64)
+    ids = np.concatenate([[0, 1, 2], (np.array(ids1[3:], dtype=np.int64)[None, :] + off[:, None]).reshape(-1)])
+    last = tuple(int(v) + per * (units - 1) for v in last1)
+    return var.astype(np.uint32), cols, 3 + per * units, ids, last, tuple(last1), pts
+
+
+def main_ecc(args, reps):
+    from circuits import jj_add
+    from pnp import abi
+    from pnp_testlib import fr_mont, ints_to_arr
+    import torch
+    import pnp
+    t0 = time.perf_counter()
+    tpl = ecc_circuit(1)
+    want, got = ecc_circuit(3), ecc_circuit(3, tpl)
+    assert np.array_equal(want[0], got[0]) and want[2] == got[2] and list(want[3]) == list(got[3])
+    assert all(np.array_equal(want[1][k], got[1][k]) for k in ECC_SELECTORS) and tuple(want[4]) == tuple(got[4])
+    base, start = tpl[6]
+    build_s = time.perf_counter() - t0
+    if not torch.cuda.is_available():
+        raise SystemExit("solve_time: no GPU (a measurement needs one; nothing is written)")
+    to_int = lambda limbs: sum(int(w) << (64 * k) for k, w in enumerate(limbs))
+    result = {"circuit": "K units: s = p + q, fixed_base_scalar_mul(s, B) over 255 rows, point_addition_gate(running "
+                         "point, s B); composer layout", "inverse": args.inverse, "by_k": {}}
+    for units in (1, 1024):
+        var, cols, n_vars, ids, last, first_sum, _ = ecc_circuit(units, tpl)
+        ng = var.shape[1]
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        rng = np.random.default_rng(args.seed)
+        vals = [0, start[0], start[1]] + [int.from_bytes(rng.bytes(32), "little") >> 4 for _ in range(len(ids) - 3)]
+        inputs = ints_to_arr([fr_mont(v) for v in vals])
+        desc = abi.CircuitDesc(n_gates=ng, n_vars=n_vars, lookup_len=0)
+        var = np.ascontiguousarray(var)
+        for j in range(4):
+            desc.var[j] = var[j].ctypes.data_as(abi.U32P)
+        for k, name in enumerate(abi.DESC_SELECTORS):
+            if name in cols and cols[name].any():
+                desc.sel[k] = cols[name].ctypes.data_as(abi.U64P)
+        ctx = pnp.Context(0)
+        ctx.preprocess(desc, device_ptrs=False)
+        plan_s, infos = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            rc, info = ctx.load_solve_plan_ecc(ids.ctypes.data, len(ids), 0, 0, 0,
+                                               abi.SOLVE_FIXED_ADD | abi.SOLVE_VAR_ADD, False)
+            plan_s.append(time.perf_counter() - t0)
+            if rc != 0:
+                raise SystemExit(f"solve_time: no plan: {ctx.last_error()}")
+            infos.append(bytes(info))
+        if len(set(infos)) != 1 or info.n_solved + info.n_inputs != n_vars:
+            raise SystemExit("solve_time: the plan differs between builds, or does not cover every variable")
+        n_fixed, n_var = ctx.solve_ecc_entries()
+
+        def solve():
+            t0 = time.perf_counter()
+            ctx.solve_assignment(inputs.ctypes.data, len(ids), False)
+            return time.perf_counter() - t0, dict(ctx.stage_times())
+
+        solve()
+        ok, rep = ctx.check_solved([])
+        if not ok:
+            raise SystemExit(f"solve_time: the solution fails the check: {ctx.last_error()}")
+        # the first unit's sum: start + (p + q) B by double and add
+        k, acc, dbl = vals[3] + vals[4], (0, 1), base
+        while k:
+            if k & 1:
+                acc = jj_add(acc, dbl)
+            dbl, k = jj_add(dbl, dbl), k >> 1
+        expect = jj_add(start, acc)
+        got_pt = tuple(to_int(l) for l in ctx.assignment_values(ids=[int(v) for v in first_sum]))
+        if got_pt != tuple(fr_mont(c) for c in expect):
+            raise SystemExit("solve_time: the first unit's point is not Python's")
+        runs = [solve() for _ in range(reps)]
+        ctx.kernel_timing(True)
+        solve()
+        levels_ms, _ = ctx.kernel_stats("solve_levels")
+        ctx.kernel_timing(False)
+        ctx.close()
+        result["by_k"][str(units)] = {
+            "lg": max(4, int(ng).bit_length()), "n_gates": int(ng), "n_vars": int(n_vars),
+            "n_inputs": int(info.n_inputs), "n_solved": int(info.n_solved), "n_levels": int(info.n_levels),
+            "max_width": int(info.max_width),
+            "defined": {"arithmetic": int(info.n_solved) - n_fixed - n_var, "fixed_add": int(n_fixed),
+                        "var_add": int(n_var)},
+            "plan_bytes": int(info.plan_bytes), "solution_passes_check_solved": True,
+            "plan_build_ms_runs": [round(1e3 * x, 2) for x in plan_s], "plan_build_ms": round(1e3 * median(plan_s), 2),
+            "solve_ms_runs": [round(1e3 * t, 3) for t, _ in runs], "solve_ms": round(1e3 * median([t for t, _ in runs]), 3),
+            "levels_kernels_ms": round(levels_ms, 3), "reps": reps,
+        }
+    result["host_build_s"] = round(build_s, 2)
+    out = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            out = json.load(f)
+    out[args.inverse] = result
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=15)
@@ -477,12 +634,19 @@ def main():
     ap.add_argument("--gates", action="store_true",
                     help="range and logic rows that define: a synthetic circuit of range checks and XORs on 2^lg")
     ap.add_argument("--lg", type=int, default=20, help="--gates: the domain")
+    ap.add_argument("--ecc", action="store_true",
+                    help="fixed-base and curve-addition rows that define: K 255-bit multiplications, K = 1 and 1024")
+    ap.add_argument("--inverse", default="binary", choices=["binary", "fermat"],
+                    help="--ecc: the inversion the loaded library was built with (the key the result is filed under)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     reps = max(args.reps, 5)
     if args.out is None:
-        name = "solve_gates_time.json" if args.gates else "solve_outputs_time.json" if args.outputs else "solve_time.json"
+        name = ("solve_ecc_time.json" if args.ecc else "solve_gates_time.json" if args.gates
+                else "solve_outputs_time.json" if args.outputs else "solve_time.json")
         args.out = os.path.join(REPO, "profiles", name)
+    if args.ecc:
+        return main_ecc(args, reps)
     if args.gates:
         return main_gates(args, reps)
     if args.outputs:

@@ -364,6 +364,8 @@ struct SolveSel {
     // the gate families of pnp_load_solve_plan_gates: nullptr = the family's
     // flag is not set, or the key has no such rows
     const uint64_t *range, *logic;
+    // the ECC families of pnp_load_solve_plan_ecc, likewise
+    const uint64_t *fixed_add, *var_add;
 };
 // A plan in HBM, level order: entry p defines variable tgt[p] from row row[p] as
 //   q_l' a + q_r' b + q_o' c + q_4' d + q_hl' a^5 + q_hr' b^5 + q_h4' d^5 + q_m' a b + q_c' + pik PI_row,
@@ -402,6 +404,11 @@ struct SolveBuild {
     std::vector<uint32_t> gate_widths;  // gate entries of each level (as many levels; all zero without gate rows)
     uint64_t n_range = 0, n_logic = 0;  // gate entries by the family of the row that defines them
     uint64_t n_two = 0;                 // gate entries that read two values (the others read one)
+    // pnp_load_solve_plan_ecc: the fixed-add scalar definitions are gate entries
+    // (counted in gate_widths and in n_fixed); the other ECC definitions are
+    // entries of their own, ecc_widths a level, defining ecc_vars variables
+    std::vector<uint32_t> ecc_widths, ecc_vars;
+    uint64_t n_fixed = 0, n_var = 0;    // variables fixed-add rows, var-add rows define
     uint64_t n_undetermined = 0;
     uint32_t first_undetermined = 0xffffffffu;
 };
@@ -413,8 +420,9 @@ struct SolveBuild {
 //   kSolveGateProd   (A & 3) (B & 3)     (logic c_i)
 //   kSolveGateAnd    (A >> shift) & (B >> shift)
 //   kSolveGateXor    (A >> shift) ^ (B >> shift), minus r when that reaches r
+//   kSolveGateNaf    (A - s) / 2, s the lowest width-2 NAF digit of A (fixed-add d)
 // Level l is entries lvl_off[l] .. lvl_off[l + 1].
-enum { kSolveGateShift, kSolveGateProd, kSolveGateAnd, kSolveGateXor };
+enum { kSolveGateShift, kSolveGateProd, kSolveGateAnd, kSolveGateXor, kSolveGateNaf };
 struct SolveGateView {
     uint32_t *tgt, *a, *b, *word, *lvl_off;
     static uint64_t bytes(uint64_t n, uint64_t n_levels) {
@@ -425,9 +433,39 @@ struct SolveGateView {
         tgt = static_cast<uint32_t *>(base), a = tgt + nn, b = tgt + 2 * nn, word = tgt + 3 * nn, lvl_off = tgt + 4 * nn;
     }
 };
-// The (row, role) of a bid and of a definition: 16 row + role, the least wins.
-// Roles: the arithmetic slots a..d, then range a..d, then logic a, b, c, d, d_next
-enum { kSolveRoleRange = 4, kSolveRoleLogic = 8, kSolveRoles = 13 };
+// The ECC entries of a plan (fixed-add xy and point, var-add), in arrays of
+// their own, level order, by (row, kind) within a level.  Entry e, read 16
+// bytes at a time: tgt[e] = three target variables (~0: not won, or none) and
+// the kind; src[e] = four source variables; q[0..2][e] = q_l, q_r, q_c of the
+// row (Montgomery; zero for a var-add entry).  With bit = d_next - 2 d:
+//   kSolveEccXy     src = d, d_next of the row and the next:   t0 = bit q_c
+//   kSolveEccPoint  src = a, b, d, d_next: x = q_l bit, y = bit^2 (q_r - 1) + 1,
+//                   m = (bit q_c) a b D:   t0 = (x b + y a) / (1 + m),
+//                   t1 = (y b - A x a) / (1 - m)
+//   kSolveEccVar    src = a, b, c, d of the row: n = a d, t = D n (b c):
+//                   t0 = (n + b c) / (1 + t), t1 = (b d - A a c) / (1 - t), t2 = n
+// one inversion of (1 + m)(1 - m) an entry, a zero factor left out of it and
+// its quotient zero.  Level l is entries lvl_off[l] .. lvl_off[l + 1].
+enum { kSolveEccXy, kSolveEccPoint, kSolveEccVar, kSolveEccKinds };
+struct SolveEccView {
+    uint4 *tgt, *src;
+    uint64_t *q[3];
+    uint32_t *lvl_off;
+    static uint64_t bytes(uint64_t n, uint64_t n_levels) {
+        return (32 + 96) * SolveView::padded(n) + 4 * SolveView::padded(n_levels + 1);
+    }
+    void lay(void *base, uint64_t n) {
+        const uint64_t nn = SolveView::padded(n);
+        for (int c = 0; c < 3; c++) q[c] = static_cast<uint64_t *>(base) + 4 * nn * c;
+        tgt = reinterpret_cast<uint4 *>(q[2] + 4 * nn), src = tgt + nn;
+        lvl_off = reinterpret_cast<uint32_t *>(src + nn);
+    }
+};
+// The (row, role) of a bid and of a definition: 32 row + role, the least wins.
+// Roles: the arithmetic slots a..d, then range a..d, then logic a, b, c, d,
+// d_next, then fixed-add d, c, a_next, b_next, then var-add a_next, b_next, d_next
+enum { kSolveRoleRange = 4, kSolveRoleLogic = 8, kSolveRoleFixed = 13, kSolveRoleVar = 17, kSolveRoles = 20,
+       kSolveRoleBits = 5 };
 // level[u] = 0 for the n_inputs listed variables (UNSET before); returns the
 // lowest id >= n_vars in err[0], the lowest id listed twice in err[1] (~0: none)
 void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars, uint32_t *d_level, uint32_t err[2],
@@ -438,21 +476,26 @@ void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars
 // zero (~0: none); the same on every run
 void solve_mark_outputs(const uint64_t *d_rows, uint64_t n_out, uint64_t n_gates, const uint64_t *q_arith,
                         uint32_t *d_bits, uint64_t err[3], DevBuf &scratch, hipStream_t s);
-// the rounds: d_level[u] = the round that defines u (1-based), d_def[u] = 16 row
+// the rounds: d_level[u] = the round that defines u (1-based), d_def[u] = 32 row
 // + role of the rule that defines it (row: the row whose rule fires); d_level /
 // d_def: n_vars u32, d_level as solve_mark_inputs left it.  A row of d_out_bits
 // (solve_mark_outputs; nullptr: no outputs) is never looked at.  sel.range /
-// sel.logic switch the gate rules on (n_gates < 2^28).  Synchronous (one
-// read-back a round)
+// sel.logic / sel.fixed_add / sel.var_add switch the gate rules on (n_gates <
+// 2^27).  ecc_level (with an ECC family on: 3 n_gates u32, allocated here):
+// the round in which rule kind k of row i defined something at [3 i + k], 0 for
+// none.  Synchronous (one read-back a round)
 void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
-                  const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s);
+                  const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, DevBuf &ecc_level, SolveBuild &out,
+                  hipStream_t s);
 // the plan's entries in (level, variable id) order from d_level / d_def; the
 // inversions by k_batch_inverse; then the entries of the n_out output rows
 // d_out_rows.  `v` laid over a buffer of SolveView::bytes; `g` (read only when
-// the build has gate entries) over one of SolveGateView::bytes
+// the build has gate entries) over one of SolveGateView::bytes, `e` (ECC
+// entries, from d_ecc_level) over one of SolveEccView::bytes
 void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
-                const uint32_t *d_level, const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows,
-                uint64_t n_out, const SolveView &v, const SolveGateView &g, hipStream_t s);
+                const uint32_t *d_level, const uint32_t *d_def, const uint32_t *d_ecc_level, const SolveBuild &b,
+                const uint64_t *d_out_rows, uint64_t n_out, const SolveView &v, const SolveGateView &g,
+                const SolveEccView &e, hipStream_t s);
 // vals[ids[k]] = in[k]
 void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inputs, uint64_t *d_vals, hipStream_t s);
 // levels [l0, l1) of the plan: each level one launch when `wide`, else all of
@@ -461,13 +504,25 @@ void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inp
 void k_solve_levels(const SolveView &v, uint32_t l0, uint32_t l1, uint64_t p0, uint64_t p1, bool wide, uint64_t *d_vals,
                     const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s);
 
-// the gate entries g0 .. g1 - 1 of one level, a lane an entry
-void k_solve_gate_level(const SolveGateView &g, uint64_t g0, uint64_t g1, uint64_t *d_vals, hipStream_t s);
+// the gate entries g0 .. g1 - 1 of one level, a lane an entry; naf: the plan
+// has kSolveGateNaf entries (without them the kernels are the ones there were)
+void k_solve_gate_level(const SolveGateView &g, uint64_t g0, uint64_t g1, uint64_t *d_vals, hipStream_t s,
+                        bool naf = false);
 // levels [l0, l1) with gate entries among them, every level at most 256 entries
 // in all: one launch of one workgroup of 512, the arithmetic entries of a level
 // in its first four waves and the gate entries in the other four
 void k_solve_mixed_levels(const SolveView &v, const SolveGateView &g, uint32_t l0, uint32_t l1, uint64_t *d_vals,
-                          const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s);
+                          const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s,
+                          bool naf = false);
+
+// the ECC entries e0 .. e1 - 1 of one level, a lane an entry
+void k_solve_ecc_level(const SolveEccView &e, uint64_t e0, uint64_t e1, uint64_t *d_vals, hipStream_t s);
+// levels [l0, l1) with ECC entries among them, every level at most 256 entries
+// in all: one launch of one workgroup of 768, arithmetic entries in waves 0-3,
+// gate entries (gates: the plan has any) in waves 4-7, ECC entries in waves 8-11
+void k_solve_ecc_levels(const SolveView &v, const SolveGateView &g, bool gates, const SolveEccView &e, uint32_t l0,
+                        uint32_t l1, uint64_t *d_vals, const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi,
+                        hipStream_t s);
 
 // the derived public inputs of the plan's n_out output rows from the solved
 // values: v.out.pi[k], canonical

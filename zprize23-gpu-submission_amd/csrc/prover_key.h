@@ -210,6 +210,12 @@ struct ResidentKey {
         DevBuf gate_buf;
         SolveGateView gate_view{};
         uint64_t n_range = 0, n_logic = 0, n_two = 0;  // by family; n_two: those reading two values
+        // the entries fixed-add and var-add rows define (pnp_load_solve_plan_ecc)
+        // but for the fixed-add scalar's, which are gate entries; empty when
+        // the plan has none.  n_fixed, n_var: the variables each family defines
+        DevBuf ecc_buf;
+        SolveEccView ecc_view{};
+        uint64_t n_fixed = 0, n_var = 0, n_ecc = 0, n_gate = 0;  // n_ecc, n_gate: ECC entries, gate entries
         // the output rows in listed order, and the public inputs the last solve
         // derived for them (canonical, 4 words each; empty before a solve)
         std::vector<uint64_t> out_rows, out_canon;
@@ -217,32 +223,37 @@ struct ResidentKey {
             return std::find(out_rows.begin(), out_rows.end(), row) != out_rows.end();
         }
         // the launches of a solve: one wide level (more than a workgroup,
-        // arithmetic entries p0 .. p1 and gate entries g0 .. g1 together), or a
-        // run of consecutive levels that each fit one
+        // arithmetic entries p0 .. p1, gate entries g0 .. g1 and ECC entries
+        // e0 .. e1 together), or a run of consecutive levels that each fit one
         struct Run {
             uint32_t l0, l1;
             uint64_t p0, p1, g0, g1;
             bool wide;
+            uint64_t e0 = 0, e1 = 0;
         };
         std::vector<Run> runs;
-        // from the levels' widths (arithmetic and gate entries): a level wider
-        // than a workgroup, both segments counted, alone; narrower ones in runs
+        // from the levels' widths (arithmetic, gate and ECC entries; ecc_widths
+        // empty: none): a level wider than a workgroup, all segments counted,
+        // alone; narrower ones in runs
         PNP_HIDDEN static std::vector<Run> launch_runs(const std::vector<uint32_t> &widths,
-                                                       const std::vector<uint32_t> &gate_widths) {
+                                                       const std::vector<uint32_t> &gate_widths,
+                                                       const std::vector<uint32_t> &ecc_widths = {}) {
             std::vector<Run> runs;
-            uint64_t p = 0, g = 0;
+            uint64_t p = 0, g = 0, e = 0;
             for (uint32_t l = 0; l < widths.size(); l++) {
-                const uint64_t wa = widths[l], wg = gate_widths[l];
-                const bool wide = wa + wg > 256;
+                const uint64_t wa = widths[l], wg = gate_widths[l], we = l < ecc_widths.size() ? ecc_widths[l] : 0;
+                const bool wide = wa + wg + we > 256;
                 if (!wide && !runs.empty() && !runs.back().wide) {
                     runs.back().l1 = l + 1;
                     runs.back().p1 = p + wa;
                     runs.back().g1 = g + wg;
+                    runs.back().e1 = e + we;
                 } else {
-                    runs.push_back({l, l + 1, p, p + wa, g, g + wg, wide});
+                    runs.push_back({l, l + 1, p, p + wa, g, g + wg, wide, e, e + we});
                 }
                 p += wa;
                 g += wg;
+                e += we;
             }
             return runs;
         }
@@ -251,8 +262,10 @@ struct ResidentKey {
             loaded = false;
             n_inputs = n_solved = n_levels = 0;
             n_range = n_logic = n_two = 0;
+            n_fixed = n_var = n_ecc = n_gate = 0;
             buf.release();
             gate_buf.release();
+            ecc_buf.release();
             runs.clear();
             out_rows.clear();
             out_canon.clear();

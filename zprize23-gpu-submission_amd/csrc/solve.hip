@@ -13,9 +13,9 @@
 //   k_solve_ready_   round t, a lane a row not yet finished: the relevant slots
 //                    whose variable is unknown; none left: the row is finished
 //                    (its byte is cleared); exactly one, solvable: the row
-//                    bids for it, atomicMin of 16 row + slot on winner[u]
+//                    bids for it, atomicMin of 32 row + slot on winner[u]
 //   k_solve_commit_  the same rows again: the bidder that holds winner[u]
-//                    defines u (level[u] = t, def[u] = 16 row + slot).  "Known"
+//                    defines u (level[u] = t, def[u] = 32 row + slot).  "Known"
 //                    is level[u] < t here, so the levels written by other
 //                    lanes of this launch change nothing any lane decides
 //   the variables are then sorted by level (preprocess.hip's stable radix
@@ -43,15 +43,30 @@
 // Range and logic rows (pnp_load_solve_plan_gates): a second byte a row
 // (k_solve_mask_) says which gate rules the row still has; a ready gate row
 // bids for up to five variables, one of them in the next row, so a bid and a
-// definition are 16 row + role (atomicMin: the least (row, role) wins) and the
+// definition are 32 row + role (atomicMin: the least (row, role) wins) and the
 // commit counts what each family defined.  Their entries (16 bytes: target, two
 // sources, kind and shift; k_solve_gate_emit_) live in arrays of their own, and
 // run in lanes of their own: k_solve_gate_wide_ a lane an entry of one level,
 // k_solve_mixed_ one workgroup of 512 over a run of narrow levels, arithmetic
 // entries in waves 0-3 and gate entries in waves 4-7, so that no wave runs both
 // bodies.  Plans without gate entries launch what they always launched.
+//
+// Fixed-base and curve-addition rows (pnp_load_solve_plan_ecc): four more bits
+// of the second byte (the fixed-add scalar, xy and point rules, the var-add
+// rule) and seven more roles, so a bid is 32 row + role.  The rounds' kernels
+// are instantiated on "the plan has ECC rules": without them the bodies are the
+// ones above.  The scalar definition is one more kind of gate entry (integer
+// work on one canonical value); the others are ECC entries (SolveEccView): the
+// commit notes the round of every (row, kind) that defined something, those
+// are sorted by round, and k_solve_ecc_emit_ writes an entry for each with
+// the targets it won and the row's q_l, q_r, q_c.  A solve runs them in lanes of
+// their own: k_solve_ecc_wide_ a lane an entry of one level, k_solve_ecc_mixed_
+// one workgroup of 768 over a run of narrow levels, ECC entries in waves 8-11.
+// An entry inverts once, (1 + m)(1 - m), by kEccInverseBinary's choice of
+// inverse() (Fermat) or fr_inverse_bin (binary Euclid); inv(0) = 0 in both.
 // No LDS, no scalar-memory tricks; plain C++ and vector memory operations.
 #include "pnp_internal.h"
+#include "widgets.cuh"
 
 namespace pnp {
 
@@ -90,10 +105,14 @@ __device__ __forceinline__ uint32_t row_mask(const SolveSel &q, uint64_t i) {
 
 // the gate rules of row i: kGateRange, kGateLogic (with kGateXor: q_c = -1, else
 // q_c = 1; a logic row with another q_c has no rule), none on the last row
-enum : uint32_t { kGateRange = 1, kGateLogic = 2, kGateXor = 4 };
+// kFixScalar, kFixXy, kFixPoint: the three rules of a fixed-add row; kVarAdd
+enum : uint32_t { kGateRange = 1, kGateLogic = 2, kGateXor = 4, kFixScalar = 8, kFixXy = 16, kFixPoint = 32,
+                  kVarAdd = 64, kEccRules = kFixScalar | kFixXy | kFixPoint | kVarAdd };
 __device__ __forceinline__ uint32_t row_gates(const SolveSel &q, uint64_t i, uint64_t n_gates) {
     if (i + 1 >= n_gates) return 0;
     uint32_t r = nz(q.range, i) ? kGateRange : 0;
+    if (nz(q.fixed_add, i)) r |= kFixScalar | kFixXy | kFixPoint;
+    if (nz(q.var_add, i)) r |= kVarAdd;
     if (nz(q.logic, i)) {
         const Fr c = load_fr(q.q_c, i);
         if (c == Fr::one()) r |= kGateLogic;
@@ -160,7 +179,7 @@ __device__ __forceinline__ int unknowns(const MapArgs &a, uint64_t i, uint32_t m
 // nothing left to define is cleared, and so is the bit of a gate rule none of
 // whose slots is unknown, or that is ready (whatever it bid for is defined in
 // this round, by this row or by a lower one).
-template <class Put>
+template <bool ECC, class Put>
 __device__ __forceinline__ void row_bids(const MapArgs &a, uint64_t i, uint32_t &m, uint32_t &gm, const uint32_t *level,
                                          uint32_t bound, uint64_t n_vars, Put &&put) {
     auto unknown = [&](uint32_t v) { return v < n_vars && __atomic_load_n(&level[v], __ATOMIC_RELAXED) >= bound; };
@@ -196,8 +215,50 @@ __device__ __forceinline__ void row_bids(const MapArgs &a, uint64_t i, uint32_t 
         }
         if (ready || !left) gm &= ~(kGateLogic | kGateXor);
     }
+    if constexpr (ECC) {
+        if (gm & (kFixScalar | kFixXy | kFixPoint)) {
+            const bool d0 = known(a.var[3][i]), d1 = known(a.var[3][i + 1]);
+            if (gm & kFixScalar) {
+                const uint32_t v = a.var[3][i];
+                const bool left = unknown(v);
+                if (d1 && left) put(v, (uint32_t)kSolveRoleFixed);
+                if (d1 || !left) gm &= ~kFixScalar;
+            }
+            if (gm & kFixXy) {
+                const uint32_t v = a.var[2][i];
+                const bool ready = d0 && d1, left = unknown(v);
+                if (ready && left) put(v, (uint32_t)(kSolveRoleFixed + 1));
+                if (ready || !left) gm &= ~kFixXy;
+            }
+            if (gm & kFixPoint) {
+                const bool ready = d0 && d1 && known(a.var[0][i]) && known(a.var[1][i]);
+                bool left = false;
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const uint32_t v = a.var[j][i + 1];
+                    if (!unknown(v)) continue;
+                    left = true;
+                    if (ready) put(v, (uint32_t)(kSolveRoleFixed + 2 + j));
+                }
+                if (ready || !left) gm &= ~kFixPoint;
+            }
+        }
+        if (gm & kVarAdd) {
+            const bool ready = known(a.var[0][i]) && known(a.var[1][i]) && known(a.var[2][i]) && known(a.var[3][i]);
+            bool left = false;
+#pragma unroll
+            for (int j = 0; j < 3; j++) {  // a_next, b_next, d_next
+                const uint32_t v = a.var[j < 2 ? j : 3][i + 1];
+                if (!unknown(v)) continue;
+                left = true;
+                if (ready) put(v, (uint32_t)(kSolveRoleVar + j));
+            }
+            if (ready || !left) gm &= ~kVarAdd;
+        }
+    }
 }
 
+template <bool ECC>
 __global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
                                                       const uint8_t *gmask, const uint32_t *level, uint32_t *winner) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -205,8 +266,8 @@ __global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gate
     uint32_t m = mask[i], gm = gmask ? gmask[i] : 0;
     if (!m && !gm) return;
     const uint32_t m0 = m;
-    row_bids(a, i, m, gm, level, kUnset, n_vars, [&](uint32_t u, uint32_t role) {
-        const uint32_t key = 16 * (uint32_t)i + role;
+    row_bids<ECC>(a, i, m, gm, level, kUnset, n_vars, [&](uint32_t u, uint32_t role) {
+        const uint32_t key = ((uint32_t)i << kSolveRoleBits) + role;
         if (__atomic_load_n(&winner[u], __ATOMIC_RELAXED) > key) atomicMin(&winner[u], key);
     });
     // (a ready gate rule keeps its bit until the commit, which looks at the same rows)
@@ -214,31 +275,51 @@ __global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gate
 }
 
 // count[0..3]: the round's definitions by arithmetic, range and logic rules,
-// and those of them that read two values (logic c, d, d_next)
+// and those of them that read two values (logic c, d, d_next); with ECC rules
+// count[4..7]: by the fixed-add scalar rule, by the other fixed-add rules, by
+// var-add rules, and the (row, kind) pairs those two defined anything for (the
+// ECC entries), whose round goes to ecc_level[3 row + kind]
+template <bool ECC>
 __global__ __launch_bounds__(256) void k_solve_commit_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
                                                        uint8_t *gmask, uint32_t *level, const uint32_t *winner,
-                                                       uint32_t *def, uint32_t t, uint32_t *count) {
+                                                       uint32_t *def, uint32_t t, uint32_t *count,
+                                                       uint32_t *ecc_level) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint32_t won[4] = {0, 0, 0, 0};
+    constexpr int kCounts = ECC ? 8 : 4;
+    uint32_t won[kCounts] = {};
     if (i < n_gates) {
         uint32_t m = mask[i], gm = gmask ? gmask[i] : 0;
         if (m || gm) {
             const uint32_t gm0 = gm;
-            row_bids(a, i, m, gm, level, t, n_vars, [&](uint32_t u, uint32_t role) {
-                const uint32_t key = 16 * (uint32_t)i + role;
+            uint32_t kinds = 0;
+            row_bids<ECC>(a, i, m, gm, level, t, n_vars, [&](uint32_t u, uint32_t role) {
+                const uint32_t key = ((uint32_t)i << kSolveRoleBits) + role;
                 if (winner[u] != key) return;
                 __atomic_store_n(&level[u], t, __ATOMIC_RELAXED);
                 def[u] = key;
-                won[role < kSolveRoleRange ? 0 : role < kSolveRoleLogic ? 1 : 2]++;
-                if (role >= kSolveRoleLogic + 2) won[3]++;
+                if (!ECC || role < kSolveRoleFixed) {
+                    won[role < kSolveRoleRange ? 0 : role < kSolveRoleLogic ? 1 : 2]++;
+                    if (role >= kSolveRoleLogic + 2) won[3]++;
+                } else if constexpr (ECC) {
+                    won[role == kSolveRoleFixed ? 4 : role < kSolveRoleVar ? 5 : 6]++;
+                    if (role > kSolveRoleFixed)
+                        kinds |= 1u << (role == kSolveRoleFixed + 1 ? kSolveEccXy
+                                        : role < kSolveRoleVar      ? kSolveEccPoint
+                                                                    : kSolveEccVar);
+                }
                 if (role < kSolveRoleRange) mask[i] = 0;
             });
             if (gm != gm0) gmask[i] = (uint8_t)gm;
+            if constexpr (ECC) {
+#pragma unroll
+                for (int k = 0; k < kSolveEccKinds; k++)
+                    if ((kinds >> k) & 1) ecc_level[kSolveEccKinds * i + k] = t, won[7]++;
+            }
         }
     }
     // (a lane wins at most ten times: four bits of every counter)
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
+    for (int c = 0; c < kCounts; c++) {
         if (!gmask && c) break;
         uint32_t sum = 0;
 #pragma unroll
@@ -258,7 +339,7 @@ __global__ __launch_bounds__(256) void k_solve_unset_(const uint32_t *level, uin
 }
 
 // sort key: the 0-based level of a variable an arithmetic row defines, n_levels
-// + that level for one a gate row defines (only where gate_keys: a plan with
+// + that level for one a gate entry defines (only where gate_keys: a plan with
 // gate entries), the key above all of those for every other
 __global__ __launch_bounds__(256) void k_solve_keys_(const uint32_t *level, const uint32_t *def, uint64_t n_vars,
                                                      uint32_t n_levels, bool gate_keys, uint32_t *key) {
@@ -266,7 +347,20 @@ __global__ __launch_bounds__(256) void k_solve_keys_(const uint32_t *level, cons
     if (u >= n_vars) return;
     const uint32_t l = level[u], rest = gate_keys ? 2 * n_levels : n_levels;
     if (l < 1 || l > n_levels) key[u] = rest;
-    else key[u] = gate_keys && (def[u] & 15) >= kSolveRoleRange ? n_levels + l - 1 : l - 1;
+    else {
+        const uint32_t role = def[u] & ((1u << kSolveRoleBits) - 1);
+        if (role > kSolveRoleFixed) key[u] = rest;  // (an ECC entry's: not in either array)
+        else key[u] = gate_keys && role >= kSolveRoleRange ? n_levels + l - 1 : l - 1;
+    }
+}
+
+// sort key of a (row, kind): the 0-based round in which it defined something, n_levels for none
+__global__ __launch_bounds__(256) void k_solve_ecc_keys_(const uint32_t *ecc_level, uint64_t n, uint32_t n_levels,
+                                                         uint32_t *key) {
+    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t l = ecc_level[k];
+    key[k] = l >= 1 && l <= n_levels ? l - 1 : n_levels;
 }
 
 // entry p: its target, row and wires, and the two denominators coef and coef q_arith
@@ -276,7 +370,7 @@ __global__ __launch_bounds__(256) void k_solve_denoms_(MapArgs a, SolveSel q, co
     const uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (p >= n) return;
     const uint32_t u = order[p] < n_vars ? order[p] : 0, d = def[u];
-    const uint64_t i = d >> 4;
+    const uint64_t i = d >> kSolveRoleBits;
     const int slot = (int)(d & 3);  // (an arithmetic role is its slot)
     v.tgt[p] = u;
     v.row[p] = (uint32_t)i;
@@ -345,10 +439,13 @@ __global__ __launch_bounds__(256) void k_solve_gate_emit_(MapArgs a, SolveSel q,
                                                           uint64_t n_vars, SolveGateView g) {
     const uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const uint32_t u = order[p] < n_vars ? order[p] : 0, d = def[u], role = d & 15;
-    const uint64_t i = d >> 4, nx = i + 1 < n_gates ? i + 1 : i;  // (a gate rule's row has a next row)
+    const uint32_t u = order[p] < n_vars ? order[p] : 0, d = def[u], role = d & ((1u << kSolveRoleBits) - 1);
+    const uint64_t i = d >> kSolveRoleBits, nx = i + 1 < n_gates ? i + 1 : i;  // (a gate rule's row has a next row)
     uint32_t sa, sb, kind = kSolveGateShift, shift = 2;
-    if (role < kSolveRoleLogic) {  // range a..d: d_next >> 2, 4, 6, 8
+    if (role == kSolveRoleFixed) {  // fixed-add d: (d_next - s) / 2
+        sa = sb = a.var[3][nx];
+        kind = kSolveGateNaf, shift = 1;
+    } else if (role < kSolveRoleLogic) {  // range a..d: d_next >> 2, 4, 6, 8
         sa = sb = a.var[3][nx];
         shift = 2 * (role - kSolveRoleRange + 1);
     } else {
@@ -363,6 +460,39 @@ __global__ __launch_bounds__(256) void k_solve_gate_emit_(MapArgs a, SolveSel q,
         }
     }
     g.tgt[p] = u, g.a[p] = sa, g.b[p] = sb, g.word[p] = kind | shift << 8;
+}
+
+// ECC entry p: the (row, kind) at order[p], the targets it won and the row's q_l, q_r, q_c
+__global__ __launch_bounds__(256) void k_solve_ecc_emit_(MapArgs a, SolveSel q, const uint32_t *order,
+                                                         const uint32_t *level, const uint32_t *def,
+                                                         const uint32_t *ecc_level, uint64_t n, uint64_t n_gates,
+                                                         uint64_t n_vars, SolveEccView e) {
+    const uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t rk = order[p] < kSolveEccKinds * n_gates ? order[p] : 0;
+    const uint64_t i = rk / kSolveEccKinds, nx = i + 1 < n_gates ? i + 1 : i;
+    const uint32_t kind = (uint32_t)(rk % kSolveEccKinds), t = ecc_level[rk];
+    // the variable, where this row's `role` defined it in round t
+    auto won = [&](uint32_t v, uint32_t role) {
+        return v < n_vars && level[v] == t && def[v] == ((uint32_t)i << kSolveRoleBits) + role ? v : kUnset;
+    };
+    uint4 tg = make_uint4(kUnset, kUnset, kUnset, kind), sr;
+    if (kind == kSolveEccXy) {
+        tg.x = won(a.var[2][i], kSolveRoleFixed + 1);
+        sr = make_uint4(a.var[3][i], a.var[3][nx], a.var[3][i], a.var[3][i]);
+    } else if (kind == kSolveEccPoint) {
+        tg.x = won(a.var[0][nx], kSolveRoleFixed + 2), tg.y = won(a.var[1][nx], kSolveRoleFixed + 3);
+        sr = make_uint4(a.var[0][i], a.var[1][i], a.var[3][i], a.var[3][nx]);
+    } else {
+        tg.x = won(a.var[0][nx], kSolveRoleVar), tg.y = won(a.var[1][nx], kSolveRoleVar + 1);
+        tg.z = won(a.var[3][nx], kSolveRoleVar + 2);
+        sr = make_uint4(a.var[0][i], a.var[1][i], a.var[2][i], a.var[3][i]);
+    }
+    e.tgt[p] = tg, e.src[p] = sr;
+    const bool fixed = kind != kSolveEccVar;
+    store_fr(e.q[0], p, fixed ? load_fr(q.q_l, i) : Fr::zero());
+    store_fr(e.q[1], p, fixed ? load_fr(q.q_r, i) : Fr::zero());
+    store_fr(e.q[2], p, fixed ? load_fr(q.q_c, i) : Fr::zero());
 }
 
 __global__ __launch_bounds__(256) void k_solve_scatter_(const uint32_t *ids, const uint64_t *in, uint64_t n_inputs,
@@ -423,13 +553,21 @@ __device__ __forceinline__ Fr shr_bits(const Fr &x, uint32_t sh) {
     return r;
 }
 
-// one or two values to canonical form, the quads, and back (SolveGateView)
+// one or two values to canonical form, the quads, and back (SolveGateView);
+// NAF: the plan has fixed-add scalar entries (without them: the body as it was)
+template <bool NAF>
 __device__ __forceinline__ void solve_gate_entry(const SolveGateView &g, uint64_t p, uint64_t *vals) {
     const uint32_t w = g.word[p], kind = w & 255, sh = w >> 8;
     const Fr a = from_mont(load_fr(vals, g.a[p]));
     Fr r;
     if (kind == kSolveGateShift) {
         r = shr_bits(a, sh);
+    } else if (NAF && kind == kSolveGateNaf) {
+        // A even: A / 2; A = 1 mod 4: (A - 1) / 2; A = 3 mod 4: (A + 1) / 2 <= r / 2
+        r = shr_bits(a, 1);
+        uint32_t c = (a.v[0] & 3) == 3;
+#pragma unroll
+        for (int k = 0; k < 8; k++) r.v[k] = __builtin_addc(r.v[k], 0u, c, &c);
     } else {
         const Fr b = from_mont(load_fr(vals, g.b[p]));
         if (kind == kSolveGateProd) {
@@ -447,13 +585,15 @@ __device__ __forceinline__ void solve_gate_entry(const SolveGateView &g, uint64_
     store_fr(vals, g.tgt[p], to_mont(r));
 }
 
+template <bool NAF>
 __global__ __launch_bounds__(256) void k_solve_gate_wide_(SolveGateView g, uint64_t p0, uint64_t p1, uint64_t *vals) {
     const uint64_t p = p0 + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (p < p1) solve_gate_entry(g, p, vals);
+    if (p < p1) solve_gate_entry<NAF>(g, p, vals);
 }
 
 // one workgroup of 512: levels l0 .. l1 - 1, each of at most 256 entries in all;
 // lanes 0..255 (waves 0-3) take the arithmetic entries, lanes 256..511 the gate entries
+template <bool NAF>
 __global__ __launch_bounds__(512) void k_solve_mixed_(SolveView v, SolveGateView g, uint32_t l0, uint32_t l1,
                                                       uint64_t *vals, PiList pi) {
     const bool gate = threadIdx.x >= 256;
@@ -461,7 +601,82 @@ __global__ __launch_bounds__(512) void k_solve_mixed_(SolveView v, SolveGateView
     for (uint32_t l = l0; l < l1; l++) {
         if (gate) {
             const uint64_t p = (uint64_t)g.lvl_off[l] + lane;
-            if (p < g.lvl_off[l + 1]) solve_gate_entry(g, p, vals);
+            if (p < g.lvl_off[l + 1]) solve_gate_entry<NAF>(g, p, vals);
+        } else {
+            const uint64_t p = (uint64_t)v.lvl_off[l] + lane;
+            if (p < v.lvl_off[l + 1]) solve_entry(v, p, vals, pi);
+        }
+        __syncthreads();  // the level's values: written, and visible to this workgroup
+    }
+}
+
+// Fermat's uniform ~380 products, or the binary Euclid's data-dependent ~500
+// short steps: profiles/solve_ecc_time.json has both inside the level chain
+// (-DPNP_ECC_INVERSE_BINARY=0 builds the other, for tools/solve_time.py --ecc)
+#ifndef PNP_ECC_INVERSE_BINARY
+#define PNP_ECC_INVERSE_BINARY 1
+#endif
+constexpr bool kEccInverseBinary = PNP_ECC_INVERSE_BINARY;
+__device__ __forceinline__ Fr ecc_inverse(const Fr &x) {
+    if constexpr (kEccInverseBinary) return fr_inverse_bin(x);
+    else return inverse(x);
+}
+
+// one ECC entry (SolveEccView): an xy product, or one or two quotients over one inversion
+__device__ __forceinline__ void solve_ecc_entry(const SolveEccView &e, uint64_t p, uint64_t *vals) {
+    const uint4 tg = e.tgt[p], sr = e.src[p];
+    const uint32_t kind = tg.w;
+    if (kind == kSolveEccXy) {
+        const Fr bit = load_fr(vals, sr.y) - dbl(load_fr(vals, sr.x));
+        if (tg.x != kUnset) store_fr(vals, tg.x, bit * load_fr(e.q[2], p));
+        return;
+    }
+    const Fr one = Fr::one();
+    const Fr a = load_fr(vals, sr.x), b = load_fr(vals, sr.y);
+    Fr n1, n2, m, dn;
+    if (kind == kSolveEccPoint) {
+        const Fr bit = load_fr(vals, sr.w) - dbl(load_fr(vals, sr.z));
+        const Fr x = load_fr(e.q[0], p) * bit, y = bit * bit * (load_fr(e.q[1], p) - one) + one;
+        m = bit * load_fr(e.q[2], p) * a * b * jj_coeff_d();
+        n1 = x * b + y * a;
+        n2 = y * b - jj_coeff_a() * x * a;
+    } else {
+        const Fr c = load_fr(vals, sr.z), d = load_fr(vals, sr.w), bc = b * c;
+        dn = a * d;
+        m = jj_coeff_d() * dn * bc;
+        n1 = dn + bc;
+        n2 = b * d - jj_coeff_a() * a * c;
+    }
+    // a zero denominator: its quotient is zero, and it stays out of the shared inversion
+    const Fr p1 = one + m, p2 = one - m;
+    const bool z1 = p1.is_zero(), z2 = p2.is_zero();
+    const Fr f1 = z1 ? one : p1, f2 = z2 ? one : p2;
+    const Fr inv = ecc_inverse(f1 * f2);
+    if (tg.x != kUnset) store_fr(vals, tg.x, z1 ? Fr::zero() : n1 * f2 * inv);
+    if (tg.y != kUnset) store_fr(vals, tg.y, z2 ? Fr::zero() : n2 * f1 * inv);
+    if (kind == kSolveEccVar && tg.z != kUnset) store_fr(vals, tg.z, dn);
+}
+
+__global__ __launch_bounds__(256) void k_solve_ecc_wide_(SolveEccView e, uint64_t p0, uint64_t p1, uint64_t *vals) {
+    const uint64_t p = p0 + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (p < p1) solve_ecc_entry(e, p, vals);
+}
+
+// one workgroup of 768: levels l0 .. l1 - 1, each of at most 256 entries in all;
+// lanes 0..255 the arithmetic entries, 256..511 the gate entries (gates: the
+// plan has any), 512..767 (waves 8-11) the ECC entries
+__global__ __launch_bounds__(768) void k_solve_ecc_mixed_(SolveView v, SolveGateView g, bool gates, SolveEccView e,
+                                                          uint32_t l0, uint32_t l1, uint64_t *vals, PiList pi) {
+    const uint32_t part = threadIdx.x >> 8, lane = threadIdx.x & 255;
+    for (uint32_t l = l0; l < l1; l++) {
+        if (part == 2) {
+            const uint64_t p = (uint64_t)e.lvl_off[l] + lane;
+            if (p < e.lvl_off[l + 1]) solve_ecc_entry(e, p, vals);
+        } else if (part == 1) {
+            if (gates) {
+                const uint64_t p = (uint64_t)g.lvl_off[l] + lane;
+                if (p < g.lvl_off[l + 1]) solve_gate_entry<true>(g, p, vals);
+            }
         } else {
             const uint64_t p = (uint64_t)v.lvl_off[l] + lane;
             if (p < v.lvl_off[l + 1]) solve_entry(v, p, vals, pi);
@@ -538,11 +753,17 @@ void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars
 }
 
 void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
-                  const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, SolveBuild &out, hipStream_t s) {
+                  const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, DevBuf &ecc_level, SolveBuild &out,
+                  hipStream_t s) {
     const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
-    const bool gates = sel.range || sel.logic;
-    DevBuf mask(n_gates), gmask, winner(4 * n_vars), ctr(16);
+    const bool ecc = sel.fixed_add || sel.var_add, gates = sel.range || sel.logic || ecc;
+    const size_t ctr_bytes = ecc ? 32 : 16;
+    DevBuf mask(n_gates), gmask, winner(4 * n_vars), ctr(32);
     if (gates) gmask.alloc(n_gates);
+    if (ecc) {
+        ecc_level.alloc(4 * kSolveEccKinds * n_gates);
+        PNP_HIP(hipMemsetAsync(ecc_level.p, 0, 4 * kSolveEccKinds * n_gates, s));
+    }
     uint8_t *d_mask = static_cast<uint8_t *>(mask.p), *d_gmask = static_cast<uint8_t *>(gmask.p);
     PNP_HIP(hipMemsetAsync(winner.p, 0xff, 4 * n_vars, s));
     hipLaunchKernelGGL(k_solve_mask_, dim3(nblk(n_gates)), dim3(256), 0, s, sel, n_gates, d_out_bits,
@@ -550,24 +771,39 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
     PNP_HIP(hipGetLastError());
     out.widths.clear();
     out.gate_widths.clear();
-    out.n_range = out.n_logic = out.n_two = 0;
+    out.ecc_widths.clear();
+    out.ecc_vars.clear();
+    out.n_range = out.n_logic = out.n_two = out.n_fixed = out.n_var = 0;
     // (a round defines at least one variable, so there are at most n_vars of them)
     for (uint64_t t = 1; t <= n_vars; t++) {
-        PNP_HIP(hipMemsetAsync(ctr.p, 0, 16, s));
-        hipLaunchKernelGGL(k_solve_ready_, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_gmask,
-                           d_level, winner.u32());
-        hipLaunchKernelGGL(k_solve_commit_, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_gmask,
-                           d_level, winner.u32(), d_def, (uint32_t)t, ctr.u32());
+        PNP_HIP(hipMemsetAsync(ctr.p, 0, ctr_bytes, s));
+        if (ecc) {
+            hipLaunchKernelGGL(k_solve_ready_<true>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask,
+                               d_gmask, d_level, winner.u32());
+            hipLaunchKernelGGL(k_solve_commit_<true>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask,
+                               d_gmask, d_level, winner.u32(), d_def, (uint32_t)t, ctr.u32(), ecc_level.u32());
+        } else {
+            hipLaunchKernelGGL(k_solve_ready_<false>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask,
+                               d_gmask, d_level, winner.u32());
+            hipLaunchKernelGGL(k_solve_commit_<false>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars,
+                               d_mask, d_gmask, d_level, winner.u32(), d_def, (uint32_t)t, ctr.u32(),
+                               (uint32_t *)nullptr);
+        }
         PNP_HIP(hipGetLastError());
-        uint32_t won[4] = {0, 0, 0, 0};  // arithmetic, range, logic; of those, two sources
-        PNP_HIP(hipMemcpyAsync(won, ctr.p, 16, hipMemcpyDeviceToHost, s));
+        // arithmetic, range, logic; of those, two sources; fixed-add scalar, fixed-add others, var-add; ECC entries
+        uint32_t won[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        PNP_HIP(hipMemcpyAsync(won, ctr.p, ctr_bytes, hipMemcpyDeviceToHost, s));
         PNP_HIP(hipStreamSynchronize(s));
-        if (!(won[0] + won[1] + won[2])) break;
+        if (!(won[0] + won[1] + won[2] + won[4] + won[5] + won[6])) break;
         out.widths.push_back(won[0]);
-        out.gate_widths.push_back(won[1] + won[2]);
+        out.gate_widths.push_back(won[1] + won[2] + won[4]);
+        out.ecc_widths.push_back(won[7]);
+        out.ecc_vars.push_back(won[5] + won[6]);
         out.n_range += won[1];
         out.n_logic += won[2];
         out.n_two += won[3];
+        out.n_fixed += won[4] + won[5];
+        out.n_var += won[6];
     }
     uint32_t un[2] = {0, kUnset};
     PNP_HIP(hipMemcpyAsync(ctr.p, un, 8, hipMemcpyHostToDevice, s));
@@ -580,17 +816,20 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
 }
 
 void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
-                const uint32_t *d_level, const uint32_t *d_def, const SolveBuild &b, const uint64_t *d_out_rows,
-                uint64_t n_out, const SolveView &v, const SolveGateView &g, hipStream_t s) {
+                const uint32_t *d_level, const uint32_t *d_def, const uint32_t *d_ecc_level, const SolveBuild &b,
+                const uint64_t *d_out_rows, uint64_t n_out, const SolveView &v, const SolveGateView &g,
+                const SolveEccView &e, hipStream_t s) {
     const uint32_t n_levels = (uint32_t)b.widths.size();
-    std::vector<uint32_t> off(n_levels + 1, 0), goff(n_levels + 1, 0);
+    std::vector<uint32_t> off(n_levels + 1, 0), goff(n_levels + 1, 0), eoff(n_levels + 1, 0);
     for (uint32_t l = 0; l < n_levels; l++) {
         off[l + 1] = off[l] + b.widths[l];
         goff[l + 1] = goff[l] + b.gate_widths[l];
+        eoff[l + 1] = eoff[l] + b.ecc_widths[l];
     }
-    const uint64_t n = off[n_levels], n_gate = goff[n_levels];
+    const uint64_t n = off[n_levels], n_gate = goff[n_levels], n_ecc = eoff[n_levels];
     PNP_HIP(hipMemcpyAsync(v.lvl_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, s));
     if (n_gate) PNP_HIP(hipMemcpyAsync(g.lvl_off, goff.data(), 4 * goff.size(), hipMemcpyHostToDevice, s));
+    if (n_ecc) PNP_HIP(hipMemcpyAsync(e.lvl_off, eoff.data(), 4 * eoff.size(), hipMemcpyHostToDevice, s));
     const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
     if (n_out) {  // products, not quotients: no inverse
         hipLaunchKernelGGL(k_solve_out_emit_, dim3(nblk(n_out)), dim3(256), 0, s, a, sel, d_out_rows, n_out, v.out);
@@ -620,6 +859,19 @@ void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_var
             PNP_HIP(hipGetLastError());
         }
     }
+    if (n_ecc) {  // the (row, kind) pairs by round, ties in (row, kind) order
+        const uint64_t m = kSolveEccKinds * n_gates;
+        DevBuf keys(4 * m), sort_scratch;
+        hipLaunchKernelGGL(k_solve_ecc_keys_, dim3(nblk(m)), dim3(256), 0, s, d_ecc_level, m, n_levels, keys.u32());
+        PNP_HIP(hipGetLastError());
+        int bits = 1;
+        while (bits < 32 && (n_levels >> bits)) bits++;
+        const uint32_t *order = sort_positions_u32(keys.u32(), m, bits, sort_scratch, s);
+        hipLaunchKernelGGL(k_solve_ecc_emit_, dim3(nblk(n_ecc)), dim3(256), 0, s, a, sel, order, d_level, d_def,
+                           d_ecc_level, n_ecc, n_gates, n_vars, e);
+        PNP_HIP(hipGetLastError());
+        PNP_HIP(hipStreamSynchronize(s));
+    }
     PNP_HIP(hipStreamSynchronize(s));  // (off and the scratch go out of scope)
 }
 
@@ -643,16 +895,32 @@ void k_solve_levels(const SolveView &v, uint32_t l0, uint32_t l1, uint64_t p0, u
     PNP_HIP(hipGetLastError());
 }
 
-void k_solve_gate_level(const SolveGateView &g, uint64_t g0, uint64_t g1, uint64_t *d_vals, hipStream_t s) {
+void k_solve_gate_level(const SolveGateView &g, uint64_t g0, uint64_t g1, uint64_t *d_vals, hipStream_t s, bool naf) {
     if (g1 <= g0) return;
-    hipLaunchKernelGGL(k_solve_gate_wide_, dim3(nblk(g1 - g0)), dim3(256), 0, s, g, g0, g1, d_vals);
+    if (naf) hipLaunchKernelGGL(k_solve_gate_wide_<true>, dim3(nblk(g1 - g0)), dim3(256), 0, s, g, g0, g1, d_vals);
+    else hipLaunchKernelGGL(k_solve_gate_wide_<false>, dim3(nblk(g1 - g0)), dim3(256), 0, s, g, g0, g1, d_vals);
+    PNP_HIP(hipGetLastError());
+}
+
+void k_solve_ecc_level(const SolveEccView &e, uint64_t e0, uint64_t e1, uint64_t *d_vals, hipStream_t s) {
+    if (e1 <= e0) return;
+    hipLaunchKernelGGL(k_solve_ecc_wide_, dim3(nblk(e1 - e0)), dim3(256), 0, s, e, e0, e1, d_vals);
+    PNP_HIP(hipGetLastError());
+}
+
+void k_solve_ecc_levels(const SolveView &v, const SolveGateView &g, bool gates, const SolveEccView &e, uint32_t l0,
+                        uint32_t l1, uint64_t *d_vals, const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi,
+                        hipStream_t s) {
+    const PiList pi{pi_pos, pi_val, n_pi};
+    hipLaunchKernelGGL(k_solve_ecc_mixed_, dim3(1), dim3(768), 0, s, v, g, gates, e, l0, l1, d_vals, pi);
     PNP_HIP(hipGetLastError());
 }
 
 void k_solve_mixed_levels(const SolveView &v, const SolveGateView &g, uint32_t l0, uint32_t l1, uint64_t *d_vals,
-                          const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s) {
+                          const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s, bool naf) {
     const PiList pi{pi_pos, pi_val, n_pi};
-    hipLaunchKernelGGL(k_solve_mixed_, dim3(1), dim3(512), 0, s, v, g, l0, l1, d_vals, pi);
+    if (naf) hipLaunchKernelGGL(k_solve_mixed_<true>, dim3(1), dim3(512), 0, s, v, g, l0, l1, d_vals, pi);
+    else hipLaunchKernelGGL(k_solve_mixed_<false>, dim3(1), dim3(512), 0, s, v, g, l0, l1, d_vals, pi);
     PNP_HIP(hipGetLastError());
 }
 

@@ -1,6 +1,6 @@
 // solve_witness.cpp — the witness solver's host side over the kernels of
 // solve.hip: the plan build (pnp_load_solve_inputs, pnp_load_solve_plan,
-// pnp_load_solve_plan_gates), the solve (pnp_solve_assignment) and what reads
+// pnp_load_solve_plan_gates, pnp_load_solve_plan_ecc), the solve (pnp_solve_assignment) and what reads
 // the solved assignment back (pnp_assignment_*, pnp_solved_public_inputs, the
 // prologue of pnp_prove_solved / pnp_check_solved).  abi.cpp checks the
 // arguments; the plan and the solution live in ResidentKey::SolvePlan
@@ -8,7 +8,7 @@
 //
 // A plan build, in order (PlanBuild holds its scratch):
 //   preconditions  key and wire map resident, one GPU, the old plan dropped,
-//                  fewer than 2^28 gates
+//                  fewer than 2^27 gates
 //   mark_inputs    the ids to HBM, level 0 for them; a bad or repeated id refused
 //   selector_rows  forward transforms of the resident coefficients; a gate
 //                  family's only where its flag is set
@@ -56,12 +56,12 @@ struct PlanBuild {
     pnp_ctx *const ctx;
     const char *const what;
     const uint64_t n_inputs, n_outputs;
-    const uint32_t gates;
+    const uint32_t gates, ecc;
     const int device_ptrs;
     pnp_solve_info *const info;
     hipStream_t s = nullptr;
-    uint64_t ng = 0, n_vars = 0, n_arith = 0, n_gate = 0;  // gates, variables; arithmetic and gate entries
-    DevBuf ids, level, def, small;
+    uint64_t ng = 0, n_vars = 0, n_arith = 0, n_gate = 0, n_ecc = 0;  // gates, variables; entries by kind
+    DevBuf ids, level, def, small, ecc_level;
     KeyRowValues kv{ctx, 0};
     DevBuf out_rows, out_bits;
     SolveBuild b;
@@ -96,8 +96,8 @@ void PlanBuild::preconditions() {
     ng = key.wm_gates, n_vars = key.wm_vars;
     kv.lg = log2_exact(key.n);
     key.wm_columns(dvar);
-    if (ng >= (1ULL << 28)) {  // a bid is 16 row + role in 32 bits
-        set_error("%s: %llu gates (a plan covers fewer than 2^28)", what, (unsigned long long)ng);
+    if (ng >= (1ULL << 27)) {  // a bid is 32 row + role in 32 bits
+        set_error("%s: %llu gates (a plan covers fewer than 2^27)", what, (unsigned long long)ng);
         throw Error(PNP_E_ARG);
     }
 }
@@ -125,6 +125,8 @@ void PlanBuild::selector_rows() {
     // (a family's rows: only where its flag is set and the key has the selector)
     if (gates & PNP_SOLVE_RANGE) sel.range = kv.values(kRange);
     if (gates & PNP_SOLVE_LOGIC) sel.logic = kv.values(kLogic);
+    if (ecc & PNP_SOLVE_FIXED_ADD) sel.fixed_add = kv.values(kFixedAdd);
+    if (ecc & PNP_SOLVE_VAR_ADD) sel.var_add = kv.values(kVarAdd);
 }
 
 // the output rows: checked on the device, their rows marked for the mask
@@ -145,26 +147,32 @@ void PlanBuild::mark_outputs(const uint64_t *output_rows) {
 
 // the rounds, what they found for the caller, and the undetermined refusal
 pnp_solve_info PlanBuild::rounds() {
-    solve_rounds(dvar, ng, n_vars, sel, out_bits.u32(), level.u32(), def.u32(), b, s);
+    solve_rounds(dvar, ng, n_vars, sel, out_bits.u32(), level.u32(), def.u32(), ecc_level, b, s);
     pnp_solve_info out;
     memset(&out, 0, sizeof out);
+    uint64_t n_ecc_vars = 0;  // (an ECC entry defines up to three variables)
     out.n_inputs = n_inputs;
     out.n_levels = b.widths.size();
     for (size_t l = 0; l < b.widths.size(); l++) {
         n_arith += b.widths[l];
         n_gate += b.gate_widths[l];
-        out.max_width = std::max<uint64_t>(out.max_width, (uint64_t)b.widths[l] + b.gate_widths[l]);
+        n_ecc += b.ecc_widths[l];
+        n_ecc_vars += b.ecc_vars[l];
+        out.max_width = std::max<uint64_t>(out.max_width, (uint64_t)b.widths[l] + b.gate_widths[l] + b.ecc_vars[l]);
     }
-    out.n_solved = n_arith + n_gate;
+    out.n_solved = n_arith + n_gate + n_ecc_vars;
     out.n_undetermined = b.n_undetermined;
     out.first_undetermined = b.n_undetermined ? b.first_undetermined : ~0ULL;
     if (b.n_undetermined) {
         if (info) *info = out;
-        set_error(gates ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other "
-                          "wires are known, nor by a range or logic row whose next row is (%llu such variables)"
-                        : "%s: variable %u is neither an input nor defined by an arithmetic row whose other "
-                          "wires are known (%llu such variables)",
-                  what, b.first_undetermined, (unsigned long long)b.n_undetermined);
+        const char *const fmt =
+            ecc     ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other wires are "
+                      "known, nor by a range, logic, fixed-add or var-add row that is ready (%llu such variables)"
+            : gates ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other "
+                      "wires are known, nor by a range or logic row whose next row is (%llu such variables)"
+                    : "%s: variable %u is neither an input nor defined by an arithmetic row whose other "
+                      "wires are known (%llu such variables)";
+        set_error(fmt, what, b.first_undetermined, (unsigned long long)b.n_undetermined);
         throw Error(PNP_E_ARG);
     }
     return out;
@@ -179,18 +187,25 @@ void PlanBuild::emit(pnp_solve_info &out) {
         sp.gate_buf.alloc(SolveGateView::bytes(n_gate, out.n_levels));
         sp.gate_view.lay(sp.gate_buf.p, n_gate);
     }
-    solve_emit(dvar, ng, n_vars, sel, level.u32(), def.u32(), b, out_rows.u64(), n_outputs, sp.view, sp.gate_view, s);
+    if (n_ecc) {
+        sp.ecc_buf.alloc(SolveEccView::bytes(n_ecc, out.n_levels));
+        sp.ecc_view.lay(sp.ecc_buf.p, n_ecc);
+    }
+    solve_emit(dvar, ng, n_vars, sel, level.u32(), def.u32(), ecc_level.u32(), b, out_rows.u64(), n_outputs, sp.view,
+               sp.gate_view, sp.ecc_view, s);
     if (n_inputs) PNP_HIP(hipMemcpyAsync(sp.view.ids, ids.p, 4 * n_inputs, hipMemcpyDeviceToDevice, s));
     sp.out_rows.resize(n_outputs);
     if (n_outputs) PNP_HIP(hipMemcpyAsync(sp.out_rows.data(), out_rows.p, 8 * n_outputs, hipMemcpyDeviceToHost, s));
     PNP_HIP(hipStreamSynchronize(s));
-    sp.runs = SolvePlan::launch_runs(b.widths, b.gate_widths);
+    sp.runs = SolvePlan::launch_runs(b.widths, b.gate_widths, b.ecc_widths);
     sp.n_range = b.n_range, sp.n_logic = b.n_logic, sp.n_two = b.n_two;
+    sp.n_fixed = b.n_fixed, sp.n_var = b.n_var, sp.n_ecc = n_ecc;
+    sp.n_gate = n_gate;
     sp.n_inputs = n_inputs;
     sp.n_solved = out.n_solved;
     sp.n_levels = out.n_levels;
     sp.loaded = true;
-    out.plan_bytes = sp.buf.bytes + sp.gate_buf.bytes;
+    out.plan_bytes = sp.buf.bytes + sp.gate_buf.bytes + sp.ecc_buf.bytes;
 }
 
 // One solve in flight over the resident plan.
@@ -230,22 +245,34 @@ void Solve::stage_inputs(const uint64_t *inputs, uint64_t n_inputs, int device_p
 void Solve::run_levels() {
     hipEvent_t e0 = nullptr;
     ctx->ktimer.begin("solve_levels", s, e0);
+    const bool naf = sp.n_fixed != 0;  // (fixed-add scalar entries among the gate entries)
     for (const auto &r : sp.runs) {
-        if (r.g1 == r.g0) {  // no gate entries: the arithmetic kernels alone
+        if (r.e1 != r.e0) {  // ECC entries: a launch a segment, or the three-part workgroup
+            if (r.wide) {
+                if (r.p1 > r.p0) k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, true, vals, pis.pos, pis.val, pis.n, s);
+                k_solve_gate_level(sp.gate_view, r.g0, r.g1, vals, s, naf);
+                k_solve_ecc_level(sp.ecc_view, r.e0, r.e1, vals, s);
+            } else {
+                k_solve_ecc_levels(sp.view, sp.gate_view, sp.n_gate != 0, sp.ecc_view, r.l0, r.l1, vals, pis.pos,
+                                   pis.val, pis.n, s);
+            }
+        } else if (r.g1 == r.g0) {  // no gate entries: the arithmetic kernels alone
             k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, r.wide, vals, pis.pos, pis.val, pis.n, s);
         } else if (r.wide) {  // one level, a launch a segment
             if (r.p1 > r.p0) k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, true, vals, pis.pos, pis.val, pis.n, s);
-            k_solve_gate_level(sp.gate_view, r.g0, r.g1, vals, s);
+            k_solve_gate_level(sp.gate_view, r.g0, r.g1, vals, s, naf);
         } else {
-            k_solve_mixed_levels(sp.view, sp.gate_view, r.l0, r.l1, vals, pis.pos, pis.val, pis.n, s);
+            k_solve_mixed_levels(sp.view, sp.gate_view, r.l0, r.l1, vals, pis.pos, pis.val, pis.n, s, naf);
         }
     }
     // an entry reads its coefficients and ids, four values, and writes one;
     // a gate entry reads its 16 bytes and one or two values, and writes one
     const double per_entry = 32.0 * (kSolveCoefs - (sp.view.coef[kSolveQm] ? 1 : 2)) + 4 * 6 + 32 * 5;
-    const uint64_t n_gate = sp.n_range + sp.n_logic;
+    // an ECC entry reads its 128 bytes and up to four values; every variable it defines is a value written
+    const uint64_t n_ecc_vars = sp.n_fixed + sp.n_var - (sp.n_gate - sp.n_range - sp.n_logic);
     ctx->ktimer.end("solve_levels", s, e0,
-                    per_entry * (double)(sp.n_solved - n_gate) + 80.0 * (double)n_gate + 32.0 * (double)sp.n_two);
+                    per_entry * (double)(sp.n_solved - sp.n_gate - n_ecc_vars) + 80.0 * (double)sp.n_gate +
+                        32.0 * (double)sp.n_two + 256.0 * (double)sp.n_ecc + 32.0 * (double)n_ecc_vars);
     tm.mark("solve_levels");
     ctx->ktimer.collect();
 }
@@ -263,9 +290,9 @@ void Solve::derive_outputs() {
 }  // namespace
 
 void load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, uint64_t n_inputs,
-                     const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, int device_ptrs,
+                     const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, uint32_t ecc, int device_ptrs,
                      pnp_solve_info *info) {
-    PlanBuild pb{ctx, what, n_inputs, n_outputs, gates, device_ptrs, info};
+    PlanBuild pb{ctx, what, n_inputs, n_outputs, gates, ecc, device_ptrs, info};
     pb.preconditions();
     pb.mark_inputs(input_ids);
     pb.selector_rows();
@@ -283,6 +310,16 @@ void solve_gate_entries(pnp_ctx *ctx, uint64_t out[2]) {
     }
     out[0] = sp.n_range;
     out[1] = sp.n_logic;
+}
+
+void solve_ecc_entries(pnp_ctx *ctx, uint64_t out[2]) {
+    const SolvePlan &sp = ctx->key.solve;
+    if (!sp.loaded) {
+        set_error("no solve plan resident (pnp_load_solve_plan_ecc first)");
+        throw Error(PNP_E_NOKEY);
+    }
+    out[0] = sp.n_fixed;
+    out[1] = sp.n_var;
 }
 
 void solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs,
