@@ -670,8 +670,8 @@ int pnp_check_solved(pnp_ctx *ctx, uint64_t n_pi, const uint64_t *pi_pos, const 
  *     i + 1).  This extends "the lowest row defines it" and keeps the plan the
  *     same on every run.  Arithmetic rows behave as above, output rows never
  *     bid, and a variable that nothing reaches is undetermined as above.
- * Lookup rows (a table search) still never define anything; fixed-base and
- * curve-addition rows define through pnp_load_solve_plan_ecc, below.
+ * Fixed-base and curve-addition rows define through pnp_load_solve_plan_ecc,
+ * lookup rows (a table search) through pnp_load_solve_plan_lookup, both below.
  * A gate entry is 16 bytes (target, two sources, kind and shift) in arrays of
  * their own beside the arithmetic entries, level order, by variable id within
  * a level, with their own level offsets, all counted in plan_bytes; with
@@ -768,6 +768,72 @@ int pnp_load_solve_plan_ecc(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_
                             const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates,
                             uint32_t ecc, int device_ptrs, pnp_solve_info *info /* may be NULL */);
 int pnp_solve_ecc_entries(pnp_ctx *ctx, uint64_t out[2]);
+
+/* Lookup rows that define: the output wire from a table search.  The
+ * reference's caller computes c = LookupTable::lookup(a, b, d), the first table
+ * row whose columns 0, 1 and 3 equal (a, b, d), and then calls
+ * lookup_gate(a, b, c, Some(d)): c is a function of three wires that are
+ * already known, so a circuit that XORs, adds or substitutes bytes through a
+ * table needs no looked-up value from the host.
+ *
+ * pnp_load_solve_plan_lookup is pnp_load_solve_plan_ecc with `lookup`, zero or
+ * PNP_SOLVE_LOOKUP; pnp_load_solve_plan_ecc is this call with lookup = 0: the
+ * same plan, info, plan_bytes, errors, launches and solution.  Any other
+ * lookup bit is PNP_E_ARG (the message names lookup), refused before anything
+ * resident is dropped; gates and ecc are validated as above; the flag is
+ * accepted for a key without q_lookup rows (there are then no such rows and
+ * nothing is allocated).
+ * The rule joins the ones above, in the same rounds; in round t every rule
+ * looks at K_(t-1).
+ *   LOOKUP (flag set, the key's q_lookup[i] != 0, i not an output row): READY
+ *     when the variables in slots a, b and d of row i are known and the one in
+ *     slot c is not; bids for slot c.  It reads no next row, so the last gate
+ *     row takes part.  With T the key's resident table of D rows (its
+ *     lookup_len rows, then copies of row 0: MultiSet::pad), c = T[p][2], p the
+ *     lowest row with T[p][0] = a, T[p][1] = b, T[p][3] = d, compared exactly
+ *     on 3 x 256 bits: the reference's LookupTable::lookup.  No such row:
+ *     c = 0; the solve inverts nothing and cannot fail, and pnp_check_* reports
+ *     `row i: lookup constraint 0`, as it must: with no row under that key,
+ *     (a, b, 0, d) is no row of T either.  A slot c whose variable is already
+ *     known is not redefined: it stays a plain constraint for pnp_check_*.
+ *   TIES: the least (row, role) still wins; the role order goes on after
+ *     var-add's d_next with one role, lookup c.  The order of every bid of
+ *     the rules above is unchanged, so their plans are too.  A row with
+ *     q_lookup and q_arith both set follows both rules independently; on the
+ *     same row the arithmetic slot wins the tie.
+ * The plan: a lookup entry is 16 bytes, read as one 16-byte word (the target,
+ * the sources a, b, d), in an array of its own, level order, by variable id
+ * within a level, with its own level offsets.  With at least one lookup entry
+ * the plan build also indexes the table: row 0 and every row whose four
+ * columns differ from row 0's (the padding copies carry row 0's key and value
+ * and a higher index: leaving them out changes no answer), m rows, go into
+ * B = next_pow2(2 m) hash buckets by a hash of the 24 Montgomery words of their
+ * columns 0, 1, 3; the row ids are sorted by bucket with the stable radix sort,
+ * so a bucket lists its rows in ascending table order and the first exact match
+ * of a scan is the lowest row; offsets off[0..B].  The build uses no atomics:
+ * the index, like the rest of the plan, is byte for byte the same on every run.
+ * Rows that share a hash but not a key only cost time.  Entries, level offsets
+ * and index (4 (B + 1) + 4 m bytes, padded to 16) are counted in plan_bytes and
+ * dropped with the plan.  The index reads the key's resident table columns at
+ * solve time: every key load drops the wire map, and with it the plan.
+ * A level is an arithmetic, a gate, an ECC and a lookup segment: more than 256
+ * entries in all, a launch a non-empty segment; narrower levels with lookup
+ * entries share one workgroup in which the lookup entries have waves of their
+ * own (in a plan that also has ECC entries: the lanes of the gate waves after
+ * the level's gate entries).  A plan without lookup entries launches exactly
+ * what it launched before.
+ * pnp_solve_info counts every defined variable of every kind in n_solved and
+ * max_width.  pnp_solve_lookup_entries: out[0] = the variables lookup rows
+ * define in the resident plan, out[1] = the table rows in the index (0 without
+ * lookup entries); PNP_E_NOKEY without a plan.  Everything that takes a plan
+ * takes this one the same way, as listed above; the stage list is unchanged
+ * and solve_levels times every kind of entry. */
+enum { PNP_SOLVE_LOOKUP = 1 };
+int pnp_load_solve_plan_lookup(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs,
+                               const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates,
+                               uint32_t ecc, uint32_t lookup, int device_ptrs,
+                               pnp_solve_info *info /* may be NULL */);
+int pnp_solve_lookup_entries(pnp_ctx *ctx, uint64_t out[2]);
 
 /* Per-stage wall-clock (ms) of the last pnp_prove, for the bench/profiles.
  * Writes up to `cap` doubles and their names; returns the stage count. */

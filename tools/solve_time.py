@@ -63,7 +63,24 @@ The solution must pass pnp_check_solved, and the first unit's sum must be
 Python's.  --inverse names the inversion the loaded library was built with
 (csrc/solve.hip kEccInverseBinary: "binary", or "fermat" for a library built
 with -DPNP_ECC_INVERSE_BINARY=0 and given in PNP_PLONK_LIB); the result goes
-under that name, beside what the file already holds."""
+under that name, beside what the file already holds.
+
+    timeout -k 10 900 python tools/solve_time.py --lookup [--out profiles/solve_lookup_time.json]
+
+Lookup rows that define (pnp_load_solve_plan_lookup), against the 8-bit XOR
+table (LookupTable::xor_table(0, 8), 65,536 rows), two shapes:
+  wide   N units of x = p + q, y = r + s, z = lookup(x, y, -1): N independent
+         byte XORs over values the circuit computes, N chosen for D = 2^20;
+         two levels, the second one N lookup entries
+  deep   a chain of L = 4,096 lookups, z_(k+1) = lookup(z_k, b_k, -1): each
+         output is the next key, one entry a level, D = 2^16 (the table)
+Both are laid out with numpy; a three-unit (three-step) instance is asserted
+to reproduce the composer's circuit of tests/lookup_circuits.py.  The inputs
+are the p, q, r, s (z_0 and the b_k) alone.  Measured per shape: the plan build
+(three times; it includes the table index), the solve (--reps), the
+solve_levels kernels' own time, levels, entries, indexed rows and plan_bytes.
+The solution must pass pnp_check_solved and probed XORs must be Python's.  The
+result goes under "lookup", beside what the file already holds."""
 import argparse
 import json
 import os
@@ -624,6 +641,170 @@ def main_ecc(args, reps):
     print(json.dumps(result))
 
 
+LOOKUP_SELECTORS = ("q_l", "q_r", "q_o", "q_c", "q_arith", "q_lookup")
+
+
+def palette_rows(codes, values):
+    """(len(codes), 4) u64 Montgomery rows: values[codes[i]] for every i."""
+    from pnp_testlib import fr_mont, ints_to_arr
+    return np.ascontiguousarray(ints_to_arr([fr_mont(v) for v in values])[np.asarray(codes, dtype=np.int64)])
+
+
+def lookup_circuit(shape_, units, composer=False):
+    """(var (4, n_gates) u32, {selector: codes into (0, 1, -1)}, n_vars, input ids, the z ids): the wide
+    shape (units of p, q, r, s, x = p + q, y = r + s, z) or the deep one (z_0, then b_k, z_(k+1) a step);
+    variable 1 is the constant -1 of row 0.  composer: from tests/lookup_circuits.py, for the comparison."""
+    if composer:
+        from circuits import Composer
+        from ecc_circuits import constrain_to_constant
+        from gate_circuits import M1
+        from lookup_circuits import lookup_of, xor_table
+        from test_preprocess_ref import wire_map
+        cp = Composer(1)
+        cp.table = xor_table(8)
+        m1 = cp.var(M1)
+        constrain_to_constant(cp, m1, M1)
+        ids, zs = [0], []
+        z = None
+        if shape_ == "deep":
+            z = cp.var(0)
+            ids.append(z)
+        for _ in range(units):
+            if shape_ == "wide":
+                p, q, r, s = (cp.var(0) for _ in range(4))
+                x, y = cp.var(0), cp.var(0)
+                cp.row({"q_arith": 1, "q_l": 1, "q_r": 1, "q_o": M1}, p, q, x, 0)
+                cp.row({"q_arith": 1, "q_l": 1, "q_r": 1, "q_o": M1}, r, s, y, 0)
+                ids += [p, q, r, s]
+                zs.append(lookup_of(cp, x, y, m1)[1])
+            else:
+                b = cp.var(0)
+                ids.append(b)
+                z = lookup_of(cp, z, b, m1)[1]
+                zs.append(z)
+        code = {0: 0, 1: 1, M1: 2}
+        cols = {name: np.array([code[r[0].get(name, 0)] for r in cp.rows]) for name in LOOKUP_SELECTORS}
+        return wire_map(cp), cols, len(cp.vals), ids, zs
+    k = np.arange(units, dtype=np.int64)
+    if shape_ == "wide":
+        b = 2 + 7 * k  # p, q, r, s, x, y, z
+        one = np.ones(units, dtype=np.int64)
+        rows = np.stack([np.stack([b, b + 1, b + 4, 0 * k]), np.stack([b + 2, b + 3, b + 5, 0 * k]),
+                         np.stack([b + 4, b + 5, b + 6, one])], axis=2).reshape(4, -1)  # (4, units, 3) -> unit-major
+        arith = np.tile([1, 1, 0], units)
+        ids = np.concatenate([[0], (b[:, None] + np.arange(4)[None, :]).reshape(-1)])
+        n_vars, zs = 2 + 7 * units, b + 6
+    else:
+        z = 2 + 2 * k  # z_k; b_k = z_k + 1; z_(k+1) = z_k + 2
+        rows = np.stack([z, z + 1, z + 2, np.ones(units, dtype=np.int64)])
+        arith = np.zeros(units, dtype=np.int64)
+        ids = np.concatenate([[0, 2], z + 1])
+        n_vars, zs = 3 + 2 * units, z + 2
+    var = np.concatenate([np.array([[1], [0], [0], [0]]), rows], axis=1).astype(np.uint32)
+    arith = np.concatenate([[1], arith])
+    cols = {"q_arith": arith, "q_l": arith.copy(), "q_r": np.concatenate([[0], arith[1:]]),
+            "q_o": 2 * np.concatenate([[0], arith[1:]]), "q_c": np.concatenate([[1], 0 * arith[1:]]),
+            "q_lookup": 1 - arith}
+    return var, cols, n_vars, ids, zs
+
+
+def main_lookup(args, reps):
+    from pnp import abi
+    from pnp_testlib import R_MOD
+    import torch
+    import pnp
+    t0 = time.perf_counter()
+    for shape_ in ("wide", "deep"):
+        want, got = lookup_circuit(shape_, 3, composer=True), lookup_circuit(shape_, 3)
+        assert np.array_equal(want[0], got[0]) and want[2] == got[2] and list(want[3]) == list(got[3])
+        assert all(np.array_equal(want[1][k], got[1][k]) for k in LOOKUP_SELECTORS) and list(want[4]) == list(got[4])
+    byte = np.arange(256, dtype=np.int64)
+    a, b = np.repeat(byte, 256), np.tile(byte, 256)
+    pal = list(range(256)) + [R_MOD - 1]
+    table = [palette_rows(c, pal) for c in (a, b, a ^ b, np.full(65536, 256))]
+    build_s = time.perf_counter() - t0
+    if not torch.cuda.is_available():
+        raise SystemExit("solve_time: no GPU (a measurement needs one; nothing is written)")
+    to_int = lambda limbs: sum(int(w) << (64 * k) for k, w in enumerate(limbs))
+    result = {"table": "xor_table(0, 8): 65,536 rows (a, b, a ^ b, -1)", "shapes": {}}
+    for shape_, units in (("wide", ((1 << 20) - 2) // 3), ("deep", 4096)):
+        var, codes, n_vars, ids, zs = lookup_circuit(shape_, units)
+        ng = var.shape[1]
+        cols = {name: palette_rows(c, (0, 1, R_MOD - 1)) for name, c in codes.items()}
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        rng = np.random.default_rng(args.seed)
+        vals = np.concatenate([[0], rng.integers(0, 128 if shape_ == "wide" else 256, size=len(ids) - 1)])
+        inputs = palette_rows(vals, pal)
+        if shape_ == "wide":
+            v4 = vals[1:].reshape(-1, 4)
+            expect = (v4[:, 0] + v4[:, 1]) ^ (v4[:, 2] + v4[:, 3])
+        else:
+            expect = np.bitwise_xor.accumulate(vals[1:])[1:]
+        desc = abi.CircuitDesc(n_gates=ng, n_vars=n_vars, lookup_len=65536)
+        var = np.ascontiguousarray(var)
+        for j in range(4):
+            desc.var[j] = var[j].ctypes.data_as(abi.U32P)
+            desc.table[j] = table[j].ctypes.data_as(abi.U64P)
+        for k, name in enumerate(abi.DESC_SELECTORS):
+            if name in cols:
+                desc.sel[k] = cols[name].ctypes.data_as(abi.U64P)
+        ctx = pnp.Context(0)
+        ctx.preprocess(desc, device_ptrs=False)
+        plan_s, infos = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            rc, info = ctx.load_solve_plan_lookup(ids.ctypes.data, len(ids), 0, 0, 0, 0, abi.SOLVE_LOOKUP, False)
+            plan_s.append(time.perf_counter() - t0)
+            if rc != 0:
+                raise SystemExit(f"solve_time: no plan: {ctx.last_error()}")
+            infos.append(bytes(info))
+        if len(set(infos)) != 1 or info.n_solved + info.n_inputs != n_vars:
+            raise SystemExit("solve_time: the plan differs between builds, or does not cover every variable")
+        n_lookup, n_indexed = ctx.solve_lookup_entries()
+
+        def solve():
+            t0 = time.perf_counter()
+            ctx.solve_assignment(inputs.ctypes.data, len(ids), False)
+            return time.perf_counter() - t0, dict(ctx.stage_times())
+
+        solve()
+        ok, rep = ctx.check_solved([])
+        if not ok:
+            raise SystemExit(f"solve_time: the solution fails the check: {ctx.last_error()}")
+        probe = sorted(set(range(0, units, max(1, units // 64))) | {units - 1})
+        got_z = [to_int(l) for l in ctx.assignment_values(ids=[int(zs[k]) for k in probe])]
+        if got_z != [to_int(palette_rows([int(expect[k])], pal)[0]) for k in probe]:
+            raise SystemExit("solve_time: the solved XORs are not Python's")
+        runs = [solve() for _ in range(reps)]
+        ctx.kernel_timing(True)
+        solve()
+        levels_ms, _ = ctx.kernel_stats("solve_levels")
+        ctx.kernel_timing(False)
+        ctx.close()
+        result["shapes"][shape_] = {
+            "lookups": int(units), "lg": int(max(ng, 65536) - 1).bit_length(), "n_gates": int(ng), "n_vars": int(n_vars),
+            "n_inputs": int(info.n_inputs), "n_solved": int(info.n_solved), "n_levels": int(info.n_levels),
+            "max_width": int(info.max_width),
+            "defined": {"arithmetic": int(info.n_solved) - int(n_lookup), "lookup": int(n_lookup)},
+            "indexed_table_rows": int(n_indexed), "plan_bytes": int(info.plan_bytes),
+            "layout_reproduces_the_composer": True, "solution_passes_check_solved": True, "xors_probed": len(probe),
+            "plan_build_ms_runs": [round(1e3 * x, 2) for x in plan_s], "plan_build_ms": round(1e3 * median(plan_s), 2),
+            "solve_ms_runs": [round(1e3 * t, 3) for t, _ in runs], "solve_ms": round(1e3 * median([t for t, _ in runs]), 3),
+            "levels_kernels_ms": round(levels_ms, 3), "reps": reps,
+        }
+    result["host_build_s"] = round(build_s, 2)
+    out = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            out = json.load(f)
+    out["lookup"] = result
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=15)
@@ -638,13 +819,17 @@ def main():
                     help="fixed-base and curve-addition rows that define: K 255-bit multiplications, K = 1 and 1024")
     ap.add_argument("--inverse", default="binary", choices=["binary", "fermat"],
                     help="--ecc: the inversion the loaded library was built with (the key the result is filed under)")
+    ap.add_argument("--lookup", action="store_true",
+                    help="lookup rows that define: byte XORs through a table, a wide shape and a deep chain")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     reps = max(args.reps, 5)
     if args.out is None:
-        name = ("solve_ecc_time.json" if args.ecc else "solve_gates_time.json" if args.gates
+        name = ("solve_lookup_time.json" if args.lookup else "solve_ecc_time.json" if args.ecc else "solve_gates_time.json" if args.gates
                 else "solve_outputs_time.json" if args.outputs else "solve_time.json")
         args.out = os.path.join(REPO, "profiles", name)
+    if args.lookup:
+        return main_lookup(args, reps)
     if args.ecc:
         return main_ecc(args, reps)
     if args.gates:

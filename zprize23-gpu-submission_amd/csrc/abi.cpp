@@ -567,12 +567,12 @@ int pnp_last_stage_times(pnp_ctx *ctx, double *ms, const char **names, int cap) 
     return k;
 }
 
-// pnp_load_solve_plan_ecc, pnp_load_solve_plan_gates (no ECC families),
+// pnp_load_solve_plan_lookup, pnp_load_solve_plan_ecc (no lookup rule), pnp_load_solve_plan_gates (no ECC families),
 // pnp_load_solve_plan (no gate families) and pnp_load_solve_inputs (no outputs
 // either); `what` opens the messages
 static int load_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, uint64_t n_inputs,
-                     const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, uint32_t ecc, int device_ptrs,
-                     pnp_solve_info *info) {
+                     const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, uint32_t ecc, uint32_t lookup,
+                     int device_ptrs, pnp_solve_info *info) {
     if (!ctx || (n_inputs && !input_ids) || n_inputs > 0xffffffffULL || (n_outputs && !output_rows) ||
         n_outputs > 0xffffffffULL)
         return PNP_E_ARG;
@@ -584,28 +584,46 @@ static int load_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, 
         set_error("%s: ecc = 0x%x has a bit that is no ECC family (PNP_SOLVE_FIXED_ADD | PNP_SOLVE_VAR_ADD)", what, ecc);
         return PNP_E_ARG;
     }
-    PNP_TRY(load_solve_plan(ctx, what, input_ids, n_inputs, output_rows, n_outputs, gates, ecc, device_ptrs, info));
+    if (lookup & ~(uint32_t)PNP_SOLVE_LOOKUP) {
+        set_error("%s: lookup = 0x%x has a bit that is not the lookup rule (PNP_SOLVE_LOOKUP)", what, lookup);
+        return PNP_E_ARG;
+    }
+    PNP_TRY(load_solve_plan(ctx, what, input_ids, n_inputs, output_rows, n_outputs, gates, ecc, lookup, device_ptrs,
+                            info));
 }
 
 int pnp_load_solve_inputs(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, int device_ptrs,
                           pnp_solve_info *info) {
-    return load_plan(ctx, "load solve inputs", input_ids, n_inputs, nullptr, 0, 0, 0, device_ptrs, info);
+    return load_plan(ctx, "load solve inputs", input_ids, n_inputs, nullptr, 0, 0, 0, 0, device_ptrs, info);
 }
 
 int pnp_load_solve_plan(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, const uint64_t *output_rows,
                         uint64_t n_outputs, int device_ptrs, pnp_solve_info *info) {
-    return load_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, 0, 0, device_ptrs, info);
+    return load_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, 0, 0, 0, device_ptrs, info);
 }
 
 int pnp_load_solve_plan_gates(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, const uint64_t *output_rows,
                               uint64_t n_outputs, uint32_t gates, int device_ptrs, pnp_solve_info *info) {
-    return load_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, gates, 0, device_ptrs, info);
+    return load_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, gates, 0, 0, device_ptrs,
+                     info);
 }
 
 int pnp_load_solve_plan_ecc(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs, const uint64_t *output_rows,
                             uint64_t n_outputs, uint32_t gates, uint32_t ecc, int device_ptrs, pnp_solve_info *info) {
-    return load_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, gates, ecc, device_ptrs,
+    return load_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, gates, ecc, 0, device_ptrs,
                      info);
+}
+
+int pnp_load_solve_plan_lookup(pnp_ctx *ctx, const uint32_t *input_ids, uint64_t n_inputs,
+                               const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, uint32_t ecc,
+                               uint32_t lookup, int device_ptrs, pnp_solve_info *info) {
+    return load_plan(ctx, "load solve plan", input_ids, n_inputs, output_rows, n_outputs, gates, ecc, lookup,
+                     device_ptrs, info);
+}
+
+int pnp_solve_lookup_entries(pnp_ctx *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return PNP_E_ARG;
+    PNP_TRY(solve_lookup_entries(ctx, out));
 }
 
 int pnp_solve_ecc_entries(pnp_ctx *ctx, uint64_t out[2]) {

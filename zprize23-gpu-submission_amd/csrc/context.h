@@ -279,9 +279,10 @@ PNP_HIDDEN void check_witness(pnp_ctx *ctx, const CircuitC *cs, int device_ptrs,
 // ---- the witness solver (solve_witness.cpp); `what` opens the messages of a plan build ----
 PNP_HIDDEN void load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, uint64_t n_inputs,
                                 const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, uint32_t ecc,
-                                int device_ptrs, pnp_solve_info *info);
+                                uint32_t lookup, int device_ptrs, pnp_solve_info *info);
 PNP_HIDDEN void solve_gate_entries(pnp_ctx *ctx, uint64_t out[2]);
 PNP_HIDDEN void solve_ecc_entries(pnp_ctx *ctx, uint64_t out[2]);
+PNP_HIDDEN void solve_lookup_entries(pnp_ctx *ctx, uint64_t out[2]);
 PNP_HIDDEN void solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs,
                                  const ProveOpts &pis);
 PNP_HIDDEN void assignment_ptr(pnp_ctx *ctx, uint64_t **d_values, uint64_t *n_vars);

@@ -366,6 +366,8 @@ struct SolveSel {
     const uint64_t *range, *logic;
     // the ECC families of pnp_load_solve_plan_ecc, likewise
     const uint64_t *fixed_add, *var_add;
+    // the q_lookup rows of pnp_load_solve_plan_lookup, likewise
+    const uint64_t *lookup;
 };
 // A plan in HBM, level order: entry p defines variable tgt[p] from row row[p] as
 //   q_l' a + q_r' b + q_o' c + q_4' d + q_hl' a^5 + q_hr' b^5 + q_h4' d^5 + q_m' a b + q_c' + pik PI_row,
@@ -409,6 +411,9 @@ struct SolveBuild {
     // entries of their own, ecc_widths a level, defining ecc_vars variables
     std::vector<uint32_t> ecc_widths, ecc_vars;
     uint64_t n_fixed = 0, n_var = 0;    // variables fixed-add rows, var-add rows define
+    // pnp_load_solve_plan_lookup: the lookup entries of each level (one a variable), and all of them
+    std::vector<uint32_t> lookup_widths;
+    uint64_t n_lookup = 0;
     uint64_t n_undetermined = 0;
     uint32_t first_undetermined = 0xffffffffu;
 };
@@ -461,11 +466,43 @@ struct SolveEccView {
         lvl_off = reinterpret_cast<uint32_t *>(src + nn);
     }
 };
+// The lookup entries of a plan (q_lookup rows), in an array of their own, level
+// order, by variable id within a level: entry k, one uint4, is the target and
+// the sources a, b, d; the target becomes column 2 of the lowest table row whose
+// columns 0, 1, 3 equal the sources' values word for word, zero when there is
+// none.  Level l is entries lvl_off[l] .. lvl_off[l + 1].
+// The index (solve_lookup_index; a buffer of its own): a CSR over B = bmask + 1
+// hash buckets.  rows[off[h] .. off[h + 1]] are the table rows of bucket h in
+// ascending order, row 0 and every row that differs from row 0 (the padding
+// repeats row 0: the copies change no answer); t[0..3] the key's resident table
+// columns, D Montgomery rows each.
+struct SolveLookupView {
+    uint4 *ent;
+    uint32_t *lvl_off;
+    const uint32_t *off, *rows;
+    uint32_t bmask;
+    const uint64_t *t[4];
+    static uint64_t bytes(uint64_t n, uint64_t n_levels) {
+        return 16 * SolveView::padded(n) + 4 * SolveView::padded(n_levels + 1);
+    }
+    void lay(void *base, uint64_t n) {
+        ent = static_cast<uint4 *>(base);
+        lvl_off = reinterpret_cast<uint32_t *>(ent + SolveView::padded(n));
+    }
+    // m indexed rows: off[0 .. B], then rows[0 .. m - 1]
+    static uint64_t buckets(uint64_t m) {
+        uint64_t b = 2;
+        while (b < 2 * m) b <<= 1;
+        return b;
+    }
+    static uint64_t index_bytes(uint64_t m) { return 4 * SolveView::padded(buckets(m) + 1) + 4 * SolveView::padded(m); }
+};
 // The (row, role) of a bid and of a definition: 32 row + role, the least wins.
 // Roles: the arithmetic slots a..d, then range a..d, then logic a, b, c, d,
-// d_next, then fixed-add d, c, a_next, b_next, then var-add a_next, b_next, d_next
-enum { kSolveRoleRange = 4, kSolveRoleLogic = 8, kSolveRoleFixed = 13, kSolveRoleVar = 17, kSolveRoles = 20,
-       kSolveRoleBits = 5 };
+// d_next, then fixed-add d, c, a_next, b_next, then var-add a_next, b_next,
+// d_next, then lookup c
+enum { kSolveRoleRange = 4, kSolveRoleLogic = 8, kSolveRoleFixed = 13, kSolveRoleVar = 17, kSolveRoleLookup = 20,
+       kSolveRoles = 21, kSolveRoleBits = 5 };
 // level[u] = 0 for the n_inputs listed variables (UNSET before); returns the
 // lowest id >= n_vars in err[0], the lowest id listed twice in err[1] (~0: none)
 void solve_mark_inputs(const uint32_t *d_ids, uint64_t n_inputs, uint64_t n_vars, uint32_t *d_level, uint32_t err[2],
@@ -480,8 +517,8 @@ void solve_mark_outputs(const uint64_t *d_rows, uint64_t n_out, uint64_t n_gates
 // + role of the rule that defines it (row: the row whose rule fires); d_level /
 // d_def: n_vars u32, d_level as solve_mark_inputs left it.  A row of d_out_bits
 // (solve_mark_outputs; nullptr: no outputs) is never looked at.  sel.range /
-// sel.logic / sel.fixed_add / sel.var_add switch the gate rules on (n_gates <
-// 2^27).  ecc_level (with an ECC family on: 3 n_gates u32, allocated here):
+// sel.logic / sel.fixed_add / sel.var_add / sel.lookup switch the gate rules on
+// (n_gates < 2^27).  ecc_level (with an ECC family on: 3 n_gates u32, allocated here):
 // the round in which rule kind k of row i defined something at [3 i + k], 0 for
 // none.  Synchronous (one read-back a round)
 void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
@@ -491,11 +528,17 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
 // inversions by k_batch_inverse; then the entries of the n_out output rows
 // d_out_rows.  `v` laid over a buffer of SolveView::bytes; `g` (read only when
 // the build has gate entries) over one of SolveGateView::bytes, `e` (ECC
-// entries, from d_ecc_level) over one of SolveEccView::bytes
+// entries, from d_ecc_level) over one of SolveEccView::bytes, `k` (lookup
+// entries: ent and lvl_off) over one of SolveLookupView::bytes
 void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
                 const uint32_t *d_level, const uint32_t *d_def, const uint32_t *d_ecc_level, const SolveBuild &b,
                 const uint64_t *d_out_rows, uint64_t n_out, const SolveView &v, const SolveGateView &g,
-                const SolveEccView &e, hipStream_t s);
+                const SolveEccView &e, const SolveLookupView &k, hipStream_t s);
+// the table index of a plan with lookup entries over the table columns t[0..3]
+// (D rows each): counts the indexed rows m (returned), allocates `index`
+// (SolveLookupView::index_bytes(m)) and fills it, k.off / rows / bmask / t set.
+// No atomics: the same bytes on every run.  Synchronous
+uint64_t solve_lookup_index(const uint64_t *const t[4], uint64_t D, DevBuf &index, SolveLookupView &k, hipStream_t s);
 // vals[ids[k]] = in[k]
 void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inputs, uint64_t *d_vals, hipStream_t s);
 // levels [l0, l1) of the plan: each level one launch when `wide`, else all of
@@ -523,6 +566,18 @@ void k_solve_ecc_level(const SolveEccView &e, uint64_t e0, uint64_t e1, uint64_t
 void k_solve_ecc_levels(const SolveView &v, const SolveGateView &g, bool gates, const SolveEccView &e, uint32_t l0,
                         uint32_t l1, uint64_t *d_vals, const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi,
                         hipStream_t s);
+
+// the lookup entries k0 .. k1 - 1 of one level, a lane an entry
+void k_solve_lookup_level(const SolveLookupView &k, uint64_t k0, uint64_t k1, uint64_t *d_vals, hipStream_t s);
+// levels [l0, l1) with lookup entries among them, every level at most 256
+// entries in all: one launch of one workgroup, arithmetic entries in waves 0-3,
+// then (gates: the plan has gate entries) gate entries in waves 4-7, then the
+// lookup entries in four waves of their own.  ecc: the plan has
+// ECC entries; the workgroup is then k_solve_ecc_levels' 768 and the lookup
+// entries take the lanes of waves 4-7 after the level's gate entries
+void k_solve_lookup_levels(const SolveView &v, const SolveGateView &g, bool gates, const SolveEccView &e,
+                           bool ecc, const SolveLookupView &k, uint32_t l0, uint32_t l1, uint64_t *d_vals,
+                           const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s);
 
 // the derived public inputs of the plan's n_out output rows from the solved
 // values: v.out.pi[k], canonical

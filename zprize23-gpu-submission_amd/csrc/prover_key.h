@@ -216,6 +216,13 @@ struct ResidentKey {
         DevBuf ecc_buf;
         SolveEccView ecc_view{};
         uint64_t n_fixed = 0, n_var = 0, n_ecc = 0, n_gate = 0;  // n_ecc, n_gate: ECC entries, gate entries
+        // the entries lookup rows define (pnp_load_solve_plan_lookup) and the
+        // index of the key's table they search (n_indexed of its rows); both
+        // empty when the plan has no such entry.  The index reads the resident
+        // table columns: every key load drops the wire map and with it the plan
+        DevBuf lookup_buf, lookup_index;
+        SolveLookupView lookup_view{};
+        uint64_t n_lookup = 0, n_indexed = 0;
         // the output rows in listed order, and the public inputs the last solve
         // derived for them (canonical, 4 words each; empty before a solve)
         std::vector<uint64_t> out_rows, out_canon;
@@ -223,37 +230,42 @@ struct ResidentKey {
             return std::find(out_rows.begin(), out_rows.end(), row) != out_rows.end();
         }
         // the launches of a solve: one wide level (more than a workgroup,
-        // arithmetic entries p0 .. p1, gate entries g0 .. g1 and ECC entries
-        // e0 .. e1 together), or a run of consecutive levels that each fit one
+        // arithmetic entries p0 .. p1, gate entries g0 .. g1, ECC entries
+        // e0 .. e1 and lookup entries k0 .. k1 together), or a run of
+        // consecutive levels that each fit one
         struct Run {
             uint32_t l0, l1;
             uint64_t p0, p1, g0, g1;
             bool wide;
-            uint64_t e0 = 0, e1 = 0;
+            uint64_t e0 = 0, e1 = 0, k0 = 0, k1 = 0;
         };
         std::vector<Run> runs;
-        // from the levels' widths (arithmetic, gate and ECC entries; ecc_widths
-        // empty: none): a level wider than a workgroup, all segments counted,
+        // from the levels' widths (arithmetic, gate, ECC and lookup entries; ecc_widths
+        // or lookup_widths empty: none): a level wider than a workgroup, all segments counted,
         // alone; narrower ones in runs
         PNP_HIDDEN static std::vector<Run> launch_runs(const std::vector<uint32_t> &widths,
                                                        const std::vector<uint32_t> &gate_widths,
-                                                       const std::vector<uint32_t> &ecc_widths = {}) {
+                                                       const std::vector<uint32_t> &ecc_widths = {},
+                                                       const std::vector<uint32_t> &lookup_widths = {}) {
             std::vector<Run> runs;
-            uint64_t p = 0, g = 0, e = 0;
+            uint64_t p = 0, g = 0, e = 0, k = 0;
             for (uint32_t l = 0; l < widths.size(); l++) {
                 const uint64_t wa = widths[l], wg = gate_widths[l], we = l < ecc_widths.size() ? ecc_widths[l] : 0;
-                const bool wide = wa + wg + we > 256;
+                const uint64_t wk = l < lookup_widths.size() ? lookup_widths[l] : 0;
+                const bool wide = wa + wg + we + wk > 256;
                 if (!wide && !runs.empty() && !runs.back().wide) {
                     runs.back().l1 = l + 1;
                     runs.back().p1 = p + wa;
                     runs.back().g1 = g + wg;
                     runs.back().e1 = e + we;
+                    runs.back().k1 = k + wk;
                 } else {
-                    runs.push_back({l, l + 1, p, p + wa, g, g + wg, wide, e, e + we});
+                    runs.push_back({l, l + 1, p, p + wa, g, g + wg, wide, e, e + we, k, k + wk});
                 }
                 p += wa;
                 g += wg;
                 e += we;
+                k += wk;
             }
             return runs;
         }
@@ -263,6 +275,9 @@ struct ResidentKey {
             n_inputs = n_solved = n_levels = 0;
             n_range = n_logic = n_two = 0;
             n_fixed = n_var = n_ecc = n_gate = 0;
+            n_lookup = n_indexed = 0;
+            lookup_buf.release();
+            lookup_index.release();
             buf.release();
             gate_buf.release();
             ecc_buf.release();

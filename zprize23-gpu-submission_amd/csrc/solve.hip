@@ -64,6 +64,21 @@
 // one workgroup of 768 over a run of narrow levels, ECC entries in waves 8-11.
 // An entry inverts once, (1 + m)(1 - m), by kEccInverseBinary's choice of
 // inverse() (Fermat) or fr_inverse_bin (binary Euclid); inv(0) = 0 in both.
+//
+// Lookup rows (pnp_load_solve_plan_lookup): the last bit of the second byte and
+// one more role, lookup c, bid for when the row's a, b and d are known; the
+// rounds' kernels are instantiated on "the plan has the lookup rule" as well.
+// A lookup entry is one uint4 (target, sources a, b, d) in an array of its own.
+// The table index is built once with the plan (solve_lookup_index): the rows
+// that are row 0 or differ from it, sorted by a hash of their columns 0, 1, 3
+// (lookup_hash, the same function at build and at solve) with the stable radix
+// sort, so a bucket holds its rows in table order and the first exact match of
+// a scan is the reference's `position`; off[] by a lower bound a bucket.  No
+// atomics anywhere in it.  k_solve_lookup_wide_ a lane an entry of one level;
+// k_solve_lookup_mixed_ the one workgroup of the narrow levels (512 lanes, 768
+// with gate entries) with four waves for the lookup entries; a plan that has
+// ECC entries too runs k_solve_lookup_ecc_mixed_, k_solve_ecc_mixed_'s 768
+// lanes with the lookup entries in the gate waves' spare lanes.
 // No LDS, no scalar-memory tricks; plain C++ and vector memory operations.
 #include "pnp_internal.h"
 #include "widgets.cuh"
@@ -106,11 +121,13 @@ __device__ __forceinline__ uint32_t row_mask(const SolveSel &q, uint64_t i) {
 // the gate rules of row i: kGateRange, kGateLogic (with kGateXor: q_c = -1, else
 // q_c = 1; a logic row with another q_c has no rule), none on the last row
 // kFixScalar, kFixXy, kFixPoint: the three rules of a fixed-add row; kVarAdd
+// kLookup: the lookup rule (it reads no next row: the last row has it too)
 enum : uint32_t { kGateRange = 1, kGateLogic = 2, kGateXor = 4, kFixScalar = 8, kFixXy = 16, kFixPoint = 32,
-                  kVarAdd = 64, kEccRules = kFixScalar | kFixXy | kFixPoint | kVarAdd };
+                  kVarAdd = 64, kLookup = 128, kEccRules = kFixScalar | kFixXy | kFixPoint | kVarAdd };
 __device__ __forceinline__ uint32_t row_gates(const SolveSel &q, uint64_t i, uint64_t n_gates) {
-    if (i + 1 >= n_gates) return 0;
-    uint32_t r = nz(q.range, i) ? kGateRange : 0;
+    uint32_t r = nz(q.lookup, i) ? kLookup : 0;
+    if (i + 1 >= n_gates) return r;
+    if (nz(q.range, i)) r |= kGateRange;
     if (nz(q.fixed_add, i)) r |= kFixScalar | kFixXy | kFixPoint;
     if (nz(q.var_add, i)) r |= kVarAdd;
     if (nz(q.logic, i)) {
@@ -179,7 +196,7 @@ __device__ __forceinline__ int unknowns(const MapArgs &a, uint64_t i, uint32_t m
 // nothing left to define is cleared, and so is the bit of a gate rule none of
 // whose slots is unknown, or that is ready (whatever it bid for is defined in
 // this round, by this row or by a lower one).
-template <bool ECC, class Put>
+template <bool ECC, bool LK, class Put>
 __device__ __forceinline__ void row_bids(const MapArgs &a, uint64_t i, uint32_t &m, uint32_t &gm, const uint32_t *level,
                                          uint32_t bound, uint64_t n_vars, Put &&put) {
     auto unknown = [&](uint32_t v) { return v < n_vars && __atomic_load_n(&level[v], __ATOMIC_RELAXED) >= bound; };
@@ -256,9 +273,17 @@ __device__ __forceinline__ void row_bids(const MapArgs &a, uint64_t i, uint32_t 
             if (ready || !left) gm &= ~kVarAdd;
         }
     }
+    if constexpr (LK) {
+        if (gm & kLookup) {
+            const uint32_t v = a.var[2][i];
+            const bool ready = known(a.var[0][i]) && known(a.var[1][i]) && known(a.var[3][i]), left = unknown(v);
+            if (ready && left) put(v, (uint32_t)kSolveRoleLookup);
+            if (ready || !left) gm &= ~kLookup;
+        }
+    }
 }
 
-template <bool ECC>
+template <bool ECC, bool LK>
 __global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
                                                       const uint8_t *gmask, const uint32_t *level, uint32_t *winner) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -266,7 +291,7 @@ __global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gate
     uint32_t m = mask[i], gm = gmask ? gmask[i] : 0;
     if (!m && !gm) return;
     const uint32_t m0 = m;
-    row_bids<ECC>(a, i, m, gm, level, kUnset, n_vars, [&](uint32_t u, uint32_t role) {
+    row_bids<ECC, LK>(a, i, m, gm, level, kUnset, n_vars, [&](uint32_t u, uint32_t role) {
         const uint32_t key = ((uint32_t)i << kSolveRoleBits) + role;
         if (__atomic_load_n(&winner[u], __ATOMIC_RELAXED) > key) atomicMin(&winner[u], key);
     });
@@ -278,26 +303,29 @@ __global__ __launch_bounds__(256) void k_solve_ready_(MapArgs a, uint64_t n_gate
 // and those of them that read two values (logic c, d, d_next); with ECC rules
 // count[4..7]: by the fixed-add scalar rule, by the other fixed-add rules, by
 // var-add rules, and the (row, kind) pairs those two defined anything for (the
-// ECC entries), whose round goes to ecc_level[3 row + kind]
-template <bool ECC>
+// ECC entries), whose round goes to ecc_level[3 row + kind]; with the lookup
+// rule count[8]: by lookup rows
+template <bool ECC, bool LK>
 __global__ __launch_bounds__(256) void k_solve_commit_(MapArgs a, uint64_t n_gates, uint64_t n_vars, uint8_t *mask,
                                                        uint8_t *gmask, uint32_t *level, const uint32_t *winner,
                                                        uint32_t *def, uint32_t t, uint32_t *count,
                                                        uint32_t *ecc_level) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    constexpr int kCounts = ECC ? 8 : 4;
+    constexpr int kCounts = LK ? 9 : ECC ? 8 : 4;
     uint32_t won[kCounts] = {};
     if (i < n_gates) {
         uint32_t m = mask[i], gm = gmask ? gmask[i] : 0;
         if (m || gm) {
             const uint32_t gm0 = gm;
             uint32_t kinds = 0;
-            row_bids<ECC>(a, i, m, gm, level, t, n_vars, [&](uint32_t u, uint32_t role) {
+            row_bids<ECC, LK>(a, i, m, gm, level, t, n_vars, [&](uint32_t u, uint32_t role) {
                 const uint32_t key = ((uint32_t)i << kSolveRoleBits) + role;
                 if (winner[u] != key) return;
                 __atomic_store_n(&level[u], t, __ATOMIC_RELAXED);
                 def[u] = key;
-                if (!ECC || role < kSolveRoleFixed) {
+                if (LK && role == kSolveRoleLookup) {
+                    won[kCounts - 1]++;
+                } else if (!ECC || role < kSolveRoleFixed) {
                     won[role < kSolveRoleRange ? 0 : role < kSolveRoleLogic ? 1 : 2]++;
                     if (role >= kSolveRoleLogic + 2) won[3]++;
                 } else if constexpr (ECC) {
@@ -321,6 +349,7 @@ __global__ __launch_bounds__(256) void k_solve_commit_(MapArgs a, uint64_t n_gat
 #pragma unroll
     for (int c = 0; c < kCounts; c++) {
         if (!gmask && c) break;
+        if (LK && !ECC && c >= 4 && c < 8) continue;  // (no ECC rules: nothing counted there)
         uint32_t sum = 0;
 #pragma unroll
         for (int bit = 0; bit < 4; bit++) sum += (uint32_t)__popcll(__ballot((won[c] >> bit) & 1)) << bit;
@@ -493,6 +522,105 @@ __global__ __launch_bounds__(256) void k_solve_ecc_emit_(MapArgs a, SolveSel q, 
     store_fr(e.q[0], p, fixed ? load_fr(q.q_l, i) : Fr::zero());
     store_fr(e.q[1], p, fixed ? load_fr(q.q_r, i) : Fr::zero());
     store_fr(e.q[2], p, fixed ? load_fr(q.q_c, i) : Fr::zero());
+}
+
+// sort key of a variable for the lookup entries: the 0-based level of one a lookup row defines, n_levels for others
+__global__ __launch_bounds__(256) void k_solve_lookup_keys_(const uint32_t *level, const uint32_t *def, uint64_t n_vars,
+                                                            uint32_t n_levels, uint32_t *key) {
+    const uint64_t u = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (u >= n_vars) return;
+    const uint32_t l = level[u];
+    const bool mine = l >= 1 && l <= n_levels && (def[u] & ((1u << kSolveRoleBits) - 1)) == kSolveRoleLookup;
+    key[u] = mine ? l - 1 : n_levels;
+}
+
+// lookup entry p: the variable at order[p], and slots a, b, d of the row that defines it
+__global__ __launch_bounds__(256) void k_solve_lookup_emit_(MapArgs a, const uint32_t *order, const uint32_t *def,
+                                                            uint64_t n, uint64_t n_vars, uint4 *ent) {
+    const uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t u = order[p] < n_vars ? order[p] : 0;
+    const uint64_t i = def[u] >> kSolveRoleBits;
+    ent[p] = make_uint4(u, a.var[0][i], a.var[1][i], a.var[3][i]);
+}
+
+// ---- the table index of the lookup entries
+struct LookupCols {
+    const uint64_t *t[4];
+};
+
+// the bucket of a key before masking: a mix of its 24 Montgomery words (only
+// the spread over the buckets depends on it); the index build and every query
+// go through this one function
+__device__ __forceinline__ uint32_t lookup_hash(const Fr &a, const Fr &b, const Fr &d) {
+    uint32_t h = 0x9E3779B9u;
+    auto mix = [&](const Fr &x) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            h ^= x.v[k];
+            h *= 0x85EBCA6Bu;
+            h = (h << 13) | (h >> 19);
+        }
+    };
+    mix(a), mix(b), mix(d);
+    h ^= h >> 16;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 15;
+    return h;
+}
+
+// row r is indexed: row 0, and every row whose four columns are not row 0's
+__device__ __forceinline__ bool lookup_indexed(const LookupCols &t, uint64_t r) {
+    if (r == 0) return true;
+    bool same = true;
+#pragma unroll
+    for (int j = 0; j < 4; j++) same &= load_fr(t.t[j], r) == load_fr(t.t[j], 0);
+    return !same;
+}
+
+// a wave 64 rows: part[wave] = how many of them are indexed (no atomics)
+__global__ __launch_bounds__(256) void k_solve_lookup_count_(LookupCols t, uint64_t D, uint32_t *part) {
+    const uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    const unsigned long long b = __ballot(r < D && lookup_indexed(t, r));
+    if ((threadIdx.x & 63) == 0) part[r >> 6] = (uint32_t)__popcll(b);
+}
+
+// one workgroup: out[0] = the sum of part[0 .. n - 1]; a lane a stride, four
+// wave sums through part_out[1..4], added by lane 0
+__global__ __launch_bounds__(256) void k_solve_lookup_sum_(const uint32_t *part, uint64_t n, uint32_t *out) {
+    uint32_t sum = 0;
+    for (uint64_t k = threadIdx.x; k < n; k += 256) sum += part[k];
+    uint32_t wave = 0;  // (below 2^26 in all: the bits of the lanes' sums, a ballot a bit)
+    for (int bit = 0; bit < 27; bit++) wave += (uint32_t)__popcll(__ballot((sum >> bit) & 1)) << bit;
+    if ((threadIdx.x & 63) == 0) out[1 + (threadIdx.x >> 6)] = wave;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = out[1] + out[2] + out[3] + out[4];
+}
+
+// sort key of table row r: its bucket, B (above every bucket) for a row that is not indexed
+__global__ __launch_bounds__(256) void k_solve_lookup_buckets_(LookupCols t, uint64_t D, uint32_t B, uint32_t *key) {
+    const uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (r >= D) return;
+    key[r] = lookup_indexed(t, r)
+                 ? lookup_hash(load_fr(t.t[0], r), load_fr(t.t[1], r), load_fr(t.t[3], r)) & (B - 1)
+                 : B;
+}
+
+// lane x: off[x] = how many sorted rows lie in buckets below x (x <= B; off[B] =
+// m), and rows[x] = the x-th sorted row (x < m)
+__global__ __launch_bounds__(256) void k_solve_lookup_csr_(const uint32_t *key, const uint32_t *order, uint64_t D,
+                                                           uint32_t B, uint64_t m, uint32_t *off, uint32_t *rows) {
+    const uint64_t x = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (x <= B) {
+        uint64_t lo = 0, hi = D;  // the first sorted position whose key is >= x
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (key[order[mid]] < x) lo = mid + 1;
+            else hi = mid;
+        }
+        off[x] = (uint32_t)lo;
+    }
+    if (x < m) rows[x] = order[x];
 }
 
 __global__ __launch_bounds__(256) void k_solve_scatter_(const uint32_t *ids, const uint64_t *in, uint64_t n_inputs,
@@ -685,6 +813,85 @@ __global__ __launch_bounds__(768) void k_solve_ecc_mixed_(SolveView v, SolveGate
     }
 }
 
+// one lookup entry (SolveLookupView): the bucket of the three values, then its
+// rows in table order until one holds them in columns 0, 1, 3.  Values and
+// table are fully reduced Montgomery residues: the compare is on the words
+__device__ __forceinline__ void solve_lookup_entry(const SolveLookupView &k, uint64_t p, uint64_t *vals) {
+    const uint4 e = k.ent[p];
+    const Fr a = load_fr(vals, e.y), b = load_fr(vals, e.z), d = load_fr(vals, e.w);
+    const uint32_t h = lookup_hash(a, b, d) & k.bmask;
+    const uint32_t q1 = k.off[h + 1];
+    Fr c = Fr::zero();  // no such key: zero, and the check names the row
+    for (uint32_t q = k.off[h]; q < q1; q++) {
+        const uint32_t r = k.rows[q];
+        if (load_fr(k.t[0], r) == a && load_fr(k.t[1], r) == b && load_fr(k.t[3], r) == d) {
+            c = load_fr(k.t[2], r);
+            break;
+        }
+    }
+    store_fr(vals, e.x, c);
+}
+
+__global__ __launch_bounds__(256) void k_solve_lookup_wide_(SolveLookupView k, uint64_t p0, uint64_t p1,
+                                                            uint64_t *vals) {
+    const uint64_t p = p0 + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (p < p1) solve_lookup_entry(k, p, vals);
+}
+
+// one workgroup of 512 or 768 (GATE: the plan has gate entries): levels l0 ..
+// l1 - 1, each of at most 256 entries in all; lanes 0..255 the arithmetic
+// entries, then 256 lanes of gate entries (the body with the NAF kind, whether
+// or not the plan has such entries), then the lookup entries in the last four
+// waves
+template <bool GATE>
+__global__ __launch_bounds__(GATE ? 768 : 512) void k_solve_lookup_mixed_(SolveView v, SolveGateView g,
+                                                                          SolveLookupView k, uint32_t l0, uint32_t l1,
+                                                                          uint64_t *vals, PiList pi) {
+    const uint32_t part = threadIdx.x >> 8, lane = threadIdx.x & 255;
+    for (uint32_t l = l0; l < l1; l++) {
+        if (part == (GATE ? 2 : 1)) {
+            const uint64_t p = (uint64_t)k.lvl_off[l] + lane;
+            if (p < k.lvl_off[l + 1]) solve_lookup_entry(k, p, vals);
+        } else if (GATE && part == 1) {
+            const uint64_t p = (uint64_t)g.lvl_off[l] + lane;
+            if (p < g.lvl_off[l + 1]) solve_gate_entry<true>(g, p, vals);
+        } else {
+            const uint64_t p = (uint64_t)v.lvl_off[l] + lane;
+            if (p < v.lvl_off[l + 1]) solve_entry(v, p, vals, pi);
+        }
+        __syncthreads();  // the level's values: written, and visible to this workgroup
+    }
+}
+
+// the plan has ECC entries too: k_solve_ecc_mixed_'s workgroup of 768, the
+// lookup entries in the lanes of the gate waves after the level's gate entries
+// (at most 256 of both together).  A fourth part of waves would make it 1024
+// lanes, 128 registers a lane, where the ECC body has 151 in the 768-lane
+// kernel
+__global__ __launch_bounds__(768) void k_solve_lookup_ecc_mixed_(SolveView v, SolveGateView g, bool gates,
+                                                                 SolveEccView e, SolveLookupView k, uint32_t l0,
+                                                                 uint32_t l1, uint64_t *vals, PiList pi) {
+    const uint32_t part = threadIdx.x >> 8, lane = threadIdx.x & 255;
+    for (uint32_t l = l0; l < l1; l++) {
+        if (part == 2) {
+            const uint64_t p = (uint64_t)e.lvl_off[l] + lane;
+            if (p < e.lvl_off[l + 1]) solve_ecc_entry(e, p, vals);
+        } else if (part == 1) {
+            const uint32_t wg = gates ? g.lvl_off[l + 1] - g.lvl_off[l] : 0;
+            if (lane < wg) {
+                solve_gate_entry<true>(g, (uint64_t)g.lvl_off[l] + lane, vals);
+            } else {
+                const uint64_t p = (uint64_t)k.lvl_off[l] + (lane - wg);
+                if (p < k.lvl_off[l + 1]) solve_lookup_entry(k, p, vals);
+            }
+        } else {
+            const uint64_t p = (uint64_t)v.lvl_off[l] + lane;
+            if (p < v.lvl_off[l + 1]) solve_entry(v, p, vals, pi);
+        }
+        __syncthreads();  // the level's values: written, and visible to this workgroup
+    }
+}
+
 // after the last level (stream order): a lane an output row, PI = -q_arith S in canonical form
 __global__ __launch_bounds__(256) void k_solve_outputs_(SolveOutView o, uint64_t n_out, const uint64_t *vals) {
     const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -756,9 +963,10 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
                   const uint32_t *d_out_bits, uint32_t *d_level, uint32_t *d_def, DevBuf &ecc_level, SolveBuild &out,
                   hipStream_t s) {
     const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
-    const bool ecc = sel.fixed_add || sel.var_add, gates = sel.range || sel.logic || ecc;
-    const size_t ctr_bytes = ecc ? 32 : 16;
-    DevBuf mask(n_gates), gmask, winner(4 * n_vars), ctr(32);
+    const bool ecc = sel.fixed_add || sel.var_add, lk = sel.lookup != nullptr;
+    const bool gates = sel.range || sel.logic || ecc || lk;
+    const size_t ctr_bytes = lk ? 36 : ecc ? 32 : 16;
+    DevBuf mask(n_gates), gmask, winner(4 * n_vars), ctr(48);
     if (gates) gmask.alloc(n_gates);
     if (ecc) {
         ecc_level.alloc(4 * kSolveEccKinds * n_gates);
@@ -773,28 +981,28 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
     out.gate_widths.clear();
     out.ecc_widths.clear();
     out.ecc_vars.clear();
-    out.n_range = out.n_logic = out.n_two = out.n_fixed = out.n_var = 0;
+    out.lookup_widths.clear();
+    out.n_range = out.n_logic = out.n_two = out.n_fixed = out.n_var = out.n_lookup = 0;
     // (a round defines at least one variable, so there are at most n_vars of them)
     for (uint64_t t = 1; t <= n_vars; t++) {
         PNP_HIP(hipMemsetAsync(ctr.p, 0, ctr_bytes, s));
-        if (ecc) {
-            hipLaunchKernelGGL(k_solve_ready_<true>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask,
-                               d_gmask, d_level, winner.u32());
-            hipLaunchKernelGGL(k_solve_commit_<true>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask,
-                               d_gmask, d_level, winner.u32(), d_def, (uint32_t)t, ctr.u32(), ecc_level.u32());
-        } else {
-            hipLaunchKernelGGL(k_solve_ready_<false>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask,
-                               d_gmask, d_level, winner.u32());
-            hipLaunchKernelGGL(k_solve_commit_<false>, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars,
-                               d_mask, d_gmask, d_level, winner.u32(), d_def, (uint32_t)t, ctr.u32(),
-                               (uint32_t *)nullptr);
-        }
+        auto round = [&](auto ready, auto commit) {
+            hipLaunchKernelGGL(ready, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_gmask, d_level,
+                               winner.u32());
+            hipLaunchKernelGGL(commit, dim3(nblk(n_gates)), dim3(256), 0, s, a, n_gates, n_vars, d_mask, d_gmask,
+                               d_level, winner.u32(), d_def, (uint32_t)t, ctr.u32(), ecc_level.u32());
+        };
+        if (ecc && lk) round(k_solve_ready_<true, true>, k_solve_commit_<true, true>);
+        else if (lk) round(k_solve_ready_<false, true>, k_solve_commit_<false, true>);
+        else if (ecc) round(k_solve_ready_<true, false>, k_solve_commit_<true, false>);
+        else round(k_solve_ready_<false, false>, k_solve_commit_<false, false>);
         PNP_HIP(hipGetLastError());
-        // arithmetic, range, logic; of those, two sources; fixed-add scalar, fixed-add others, var-add; ECC entries
-        uint32_t won[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        // arithmetic, range, logic; of those, two sources; fixed-add scalar, fixed-add others, var-add; ECC entries;
+        // lookup
+        uint32_t won[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         PNP_HIP(hipMemcpyAsync(won, ctr.p, ctr_bytes, hipMemcpyDeviceToHost, s));
         PNP_HIP(hipStreamSynchronize(s));
-        if (!(won[0] + won[1] + won[2] + won[4] + won[5] + won[6])) break;
+        if (!(won[0] + won[1] + won[2] + won[4] + won[5] + won[6] + won[8])) break;
         out.widths.push_back(won[0]);
         out.gate_widths.push_back(won[1] + won[2] + won[4]);
         out.ecc_widths.push_back(won[7]);
@@ -804,6 +1012,8 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
         out.n_two += won[3];
         out.n_fixed += won[4] + won[5];
         out.n_var += won[6];
+        out.lookup_widths.push_back(won[8]);
+        out.n_lookup += won[8];
     }
     uint32_t un[2] = {0, kUnset};
     PNP_HIP(hipMemcpyAsync(ctr.p, un, 8, hipMemcpyHostToDevice, s));
@@ -818,18 +1028,20 @@ void solve_rounds(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_v
 void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_vars, const SolveSel &sel,
                 const uint32_t *d_level, const uint32_t *d_def, const uint32_t *d_ecc_level, const SolveBuild &b,
                 const uint64_t *d_out_rows, uint64_t n_out, const SolveView &v, const SolveGateView &g,
-                const SolveEccView &e, hipStream_t s) {
+                const SolveEccView &e, const SolveLookupView &k, hipStream_t s) {
     const uint32_t n_levels = (uint32_t)b.widths.size();
-    std::vector<uint32_t> off(n_levels + 1, 0), goff(n_levels + 1, 0), eoff(n_levels + 1, 0);
+    std::vector<uint32_t> off(n_levels + 1, 0), goff(n_levels + 1, 0), eoff(n_levels + 1, 0), koff(n_levels + 1, 0);
     for (uint32_t l = 0; l < n_levels; l++) {
         off[l + 1] = off[l] + b.widths[l];
         goff[l + 1] = goff[l] + b.gate_widths[l];
         eoff[l + 1] = eoff[l] + b.ecc_widths[l];
+        koff[l + 1] = koff[l] + b.lookup_widths[l];
     }
-    const uint64_t n = off[n_levels], n_gate = goff[n_levels], n_ecc = eoff[n_levels];
+    const uint64_t n = off[n_levels], n_gate = goff[n_levels], n_ecc = eoff[n_levels], n_lookup = koff[n_levels];
     PNP_HIP(hipMemcpyAsync(v.lvl_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, s));
     if (n_gate) PNP_HIP(hipMemcpyAsync(g.lvl_off, goff.data(), 4 * goff.size(), hipMemcpyHostToDevice, s));
     if (n_ecc) PNP_HIP(hipMemcpyAsync(e.lvl_off, eoff.data(), 4 * eoff.size(), hipMemcpyHostToDevice, s));
+    if (n_lookup) PNP_HIP(hipMemcpyAsync(k.lvl_off, koff.data(), 4 * koff.size(), hipMemcpyHostToDevice, s));
     const MapArgs a{{d_var[0], d_var[1], d_var[2], d_var[3]}};
     if (n_out) {  // products, not quotients: no inverse
         hipLaunchKernelGGL(k_solve_out_emit_, dim3(nblk(n_out)), dim3(256), 0, s, a, sel, d_out_rows, n_out, v.out);
@@ -872,7 +1084,47 @@ void solve_emit(const uint32_t *const d_var[4], uint64_t n_gates, uint64_t n_var
         PNP_HIP(hipGetLastError());
         PNP_HIP(hipStreamSynchronize(s));
     }
+    if (n_lookup) {  // the variables lookup rows define by level, ties in variable order
+        DevBuf keys(4 * n_vars), sort_scratch;
+        hipLaunchKernelGGL(k_solve_lookup_keys_, dim3(nblk(n_vars)), dim3(256), 0, s, d_level, d_def, n_vars, n_levels,
+                           keys.u32());
+        PNP_HIP(hipGetLastError());
+        int bits = 1;
+        while (bits < 32 && (n_levels >> bits)) bits++;
+        const uint32_t *order = sort_positions_u32(keys.u32(), n_vars, bits, sort_scratch, s);
+        hipLaunchKernelGGL(k_solve_lookup_emit_, dim3(nblk(n_lookup)), dim3(256), 0, s, a, order, d_def, n_lookup,
+                           n_vars, k.ent);
+        PNP_HIP(hipGetLastError());
+        PNP_HIP(hipStreamSynchronize(s));
+    }
     PNP_HIP(hipStreamSynchronize(s));  // (off and the scratch go out of scope)
+}
+
+uint64_t solve_lookup_index(const uint64_t *const t[4], uint64_t D, DevBuf &index, SolveLookupView &k, hipStream_t s) {
+    const LookupCols tc{{t[0], t[1], t[2], t[3]}};
+    const uint64_t n_part = 4 * (uint64_t)nblk(D);
+    DevBuf part(4 * n_part), total(32), keys(4 * D), sort_scratch;
+    hipLaunchKernelGGL(k_solve_lookup_count_, dim3(nblk(D)), dim3(256), 0, s, tc, D, part.u32());
+    hipLaunchKernelGGL(k_solve_lookup_sum_, dim3(1), dim3(256), 0, s, part.u32(), n_part, total.u32());
+    PNP_HIP(hipGetLastError());
+    uint32_t m32 = 0;
+    PNP_HIP(hipMemcpyAsync(&m32, total.p, 4, hipMemcpyDeviceToHost, s));
+    PNP_HIP(hipStreamSynchronize(s));
+    const uint64_t m = m32, B = SolveLookupView::buckets(m);
+    index.alloc(SolveLookupView::index_bytes(m));
+    uint32_t *off = index.u32(), *rows = off + SolveView::padded(B + 1);
+    hipLaunchKernelGGL(k_solve_lookup_buckets_, dim3(nblk(D)), dim3(256), 0, s, tc, D, (uint32_t)B, keys.u32());
+    PNP_HIP(hipGetLastError());
+    int bits = 1;
+    while (bits < 32 && (B >> bits)) bits++;  // (keys 0 .. B)
+    const uint32_t *order = sort_positions_u32(keys.u32(), D, bits, sort_scratch, s);
+    hipLaunchKernelGGL(k_solve_lookup_csr_, dim3(nblk(std::max(B + 1, m))), dim3(256), 0, s, keys.u32(), order, D,
+                       (uint32_t)B, m, off, rows);
+    PNP_HIP(hipGetLastError());
+    PNP_HIP(hipStreamSynchronize(s));  // (the scratch goes out of scope)
+    k.off = off, k.rows = rows, k.bmask = (uint32_t)(B - 1);
+    for (int j = 0; j < 4; j++) k.t[j] = t[j];
+    return m;
 }
 
 void k_solve_scatter(const uint32_t *d_ids, const uint64_t *d_in, uint64_t n_inputs, uint64_t *d_vals, hipStream_t s) {
@@ -913,6 +1165,25 @@ void k_solve_ecc_levels(const SolveView &v, const SolveGateView &g, bool gates, 
                         hipStream_t s) {
     const PiList pi{pi_pos, pi_val, n_pi};
     hipLaunchKernelGGL(k_solve_ecc_mixed_, dim3(1), dim3(768), 0, s, v, g, gates, e, l0, l1, d_vals, pi);
+    PNP_HIP(hipGetLastError());
+}
+
+void k_solve_lookup_level(const SolveLookupView &k, uint64_t k0, uint64_t k1, uint64_t *d_vals, hipStream_t s) {
+    if (k1 <= k0) return;
+    hipLaunchKernelGGL(k_solve_lookup_wide_, dim3(nblk(k1 - k0)), dim3(256), 0, s, k, k0, k1, d_vals);
+    PNP_HIP(hipGetLastError());
+}
+
+void k_solve_lookup_levels(const SolveView &v, const SolveGateView &g, bool gates, const SolveEccView &e,
+                           bool ecc, const SolveLookupView &k, uint32_t l0, uint32_t l1, uint64_t *d_vals,
+                           const uint64_t *pi_pos, const uint64_t *pi_val, uint32_t n_pi, hipStream_t s) {
+    const PiList pi{pi_pos, pi_val, n_pi};
+    if (ecc)
+        hipLaunchKernelGGL(k_solve_lookup_ecc_mixed_, dim3(1), dim3(768), 0, s, v, g, gates, e, k, l0, l1, d_vals, pi);
+    else if (gates)
+        hipLaunchKernelGGL(k_solve_lookup_mixed_<true>, dim3(1), dim3(768), 0, s, v, g, k, l0, l1, d_vals, pi);
+    else
+        hipLaunchKernelGGL(k_solve_lookup_mixed_<false>, dim3(1), dim3(512), 0, s, v, g, k, l0, l1, d_vals, pi);
     PNP_HIP(hipGetLastError());
 }
 

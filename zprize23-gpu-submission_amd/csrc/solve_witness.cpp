@@ -1,6 +1,6 @@
 // solve_witness.cpp — the witness solver's host side over the kernels of
 // solve.hip: the plan build (pnp_load_solve_inputs, pnp_load_solve_plan,
-// pnp_load_solve_plan_gates, pnp_load_solve_plan_ecc), the solve (pnp_solve_assignment) and what reads
+// pnp_load_solve_plan_gates, pnp_load_solve_plan_ecc, pnp_load_solve_plan_lookup), the solve (pnp_solve_assignment) and what reads
 // the solved assignment back (pnp_assignment_*, pnp_solved_public_inputs, the
 // prologue of pnp_prove_solved / pnp_check_solved).  abi.cpp checks the
 // arguments; the plan and the solution live in ResidentKey::SolvePlan
@@ -14,7 +14,8 @@
 //                  family's only where its flag is set
 //   mark_outputs   the output rows checked on the device, marked for the mask
 //   rounds         the levels; pnp_solve_info; an undetermined variable refused
-//   emit           the plan's entries into HBM, the ids and output rows kept
+//   emit           the plan's entries into HBM, the ids and output rows kept;
+//                  with lookup entries, the index of the key's table
 //   the launch runs (SolvePlan::launch_runs) and the counts
 // A solve, in order:
 //   preconditions  a plan, its input count, one GPU, no public input on an
@@ -56,11 +57,11 @@ struct PlanBuild {
     pnp_ctx *const ctx;
     const char *const what;
     const uint64_t n_inputs, n_outputs;
-    const uint32_t gates, ecc;
+    const uint32_t gates, ecc, lookup;
     const int device_ptrs;
     pnp_solve_info *const info;
     hipStream_t s = nullptr;
-    uint64_t ng = 0, n_vars = 0, n_arith = 0, n_gate = 0, n_ecc = 0;  // gates, variables; entries by kind
+    uint64_t ng = 0, n_vars = 0, n_arith = 0, n_gate = 0, n_ecc = 0, n_lookup = 0;  // gates, variables; entries by kind
     DevBuf ids, level, def, small, ecc_level;
     KeyRowValues kv{ctx, 0};
     DevBuf out_rows, out_bits;
@@ -127,6 +128,9 @@ void PlanBuild::selector_rows() {
     if (gates & PNP_SOLVE_LOGIC) sel.logic = kv.values(kLogic);
     if (ecc & PNP_SOLVE_FIXED_ADD) sel.fixed_add = kv.values(kFixedAdd);
     if (ecc & PNP_SOLVE_VAR_ADD) sel.var_add = kv.values(kVarAdd);
+    // (the wire map keeps the q_lookup rows, as the check reads them)
+    if (lookup & PNP_SOLVE_LOOKUP)
+        sel.lookup = ctx->key.wm_qlk.p ? ctx->key.wm_qlk.u64() : kv.values(kQlookup);
 }
 
 // the output rows: checked on the device, their rows marked for the mask
@@ -158,15 +162,19 @@ pnp_solve_info PlanBuild::rounds() {
         n_gate += b.gate_widths[l];
         n_ecc += b.ecc_widths[l];
         n_ecc_vars += b.ecc_vars[l];
-        out.max_width = std::max<uint64_t>(out.max_width, (uint64_t)b.widths[l] + b.gate_widths[l] + b.ecc_vars[l]);
+        n_lookup += b.lookup_widths[l];
+        out.max_width = std::max<uint64_t>(out.max_width, (uint64_t)b.widths[l] + b.gate_widths[l] + b.ecc_vars[l] +
+                                                              b.lookup_widths[l]);
     }
-    out.n_solved = n_arith + n_gate + n_ecc_vars;
+    out.n_solved = n_arith + n_gate + n_ecc_vars + n_lookup;
     out.n_undetermined = b.n_undetermined;
     out.first_undetermined = b.n_undetermined ? b.first_undetermined : ~0ULL;
     if (b.n_undetermined) {
         if (info) *info = out;
         const char *const fmt =
-            ecc     ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other wires are "
+            lookup  ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other wires are "
+                      "known, nor by a range, logic, fixed-add, var-add or lookup row that is ready (%llu such variables)"
+            : ecc   ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other wires are "
                       "known, nor by a range, logic, fixed-add or var-add row that is ready (%llu such variables)"
             : gates ? "%s: variable %u is neither an input nor defined by an arithmetic row whose other "
                       "wires are known, nor by a range or logic row whose next row is (%llu such variables)"
@@ -191,21 +199,34 @@ void PlanBuild::emit(pnp_solve_info &out) {
         sp.ecc_buf.alloc(SolveEccView::bytes(n_ecc, out.n_levels));
         sp.ecc_view.lay(sp.ecc_buf.p, n_ecc);
     }
+    if (n_lookup) {
+        sp.lookup_buf.alloc(SolveLookupView::bytes(n_lookup, out.n_levels));
+        sp.lookup_view.lay(sp.lookup_buf.p, n_lookup);
+        const ProverKeyC &d = ctx->key.dev;
+        const uint64_t *t[4] = {d.table1, d.table2, d.table3, d.table4};
+        if (!t[0] || !t[1] || !t[2] || !t[3]) {
+            sp.drop();
+            set_error("%s: the key has q_lookup rows and no table columns resident", what);
+            throw Error(PNP_E_ARG);
+        }
+        sp.n_indexed = solve_lookup_index(t, ctx->key.n, sp.lookup_index, sp.lookup_view, s);
+    }
     solve_emit(dvar, ng, n_vars, sel, level.u32(), def.u32(), ecc_level.u32(), b, out_rows.u64(), n_outputs, sp.view,
-               sp.gate_view, sp.ecc_view, s);
+               sp.gate_view, sp.ecc_view, sp.lookup_view, s);
     if (n_inputs) PNP_HIP(hipMemcpyAsync(sp.view.ids, ids.p, 4 * n_inputs, hipMemcpyDeviceToDevice, s));
     sp.out_rows.resize(n_outputs);
     if (n_outputs) PNP_HIP(hipMemcpyAsync(sp.out_rows.data(), out_rows.p, 8 * n_outputs, hipMemcpyDeviceToHost, s));
     PNP_HIP(hipStreamSynchronize(s));
-    sp.runs = SolvePlan::launch_runs(b.widths, b.gate_widths, b.ecc_widths);
+    sp.runs = SolvePlan::launch_runs(b.widths, b.gate_widths, b.ecc_widths, b.lookup_widths);
     sp.n_range = b.n_range, sp.n_logic = b.n_logic, sp.n_two = b.n_two;
     sp.n_fixed = b.n_fixed, sp.n_var = b.n_var, sp.n_ecc = n_ecc;
     sp.n_gate = n_gate;
+    sp.n_lookup = n_lookup;
     sp.n_inputs = n_inputs;
     sp.n_solved = out.n_solved;
     sp.n_levels = out.n_levels;
     sp.loaded = true;
-    out.plan_bytes = sp.buf.bytes + sp.gate_buf.bytes + sp.ecc_buf.bytes;
+    out.plan_bytes = sp.buf.bytes + sp.gate_buf.bytes + sp.ecc_buf.bytes + sp.lookup_buf.bytes + sp.lookup_index.bytes;
 }
 
 // One solve in flight over the resident plan.
@@ -247,7 +268,17 @@ void Solve::run_levels() {
     ctx->ktimer.begin("solve_levels", s, e0);
     const bool naf = sp.n_fixed != 0;  // (fixed-add scalar entries among the gate entries)
     for (const auto &r : sp.runs) {
-        if (r.e1 != r.e0) {  // ECC entries: a launch a segment, or the three-part workgroup
+        if (r.k1 != r.k0) {  // lookup entries: a launch a segment, or the workgroup with waves for them
+            if (r.wide) {
+                if (r.p1 > r.p0) k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, true, vals, pis.pos, pis.val, pis.n, s);
+                k_solve_gate_level(sp.gate_view, r.g0, r.g1, vals, s, naf);
+                k_solve_ecc_level(sp.ecc_view, r.e0, r.e1, vals, s);
+                k_solve_lookup_level(sp.lookup_view, r.k0, r.k1, vals, s);
+            } else {
+                k_solve_lookup_levels(sp.view, sp.gate_view, sp.n_gate != 0, sp.ecc_view, sp.n_ecc != 0,
+                                      sp.lookup_view, r.l0, r.l1, vals, pis.pos, pis.val, pis.n, s);
+            }
+        } else if (r.e1 != r.e0) {  // ECC entries: a launch a segment, or the three-part workgroup
             if (r.wide) {
                 if (r.p1 > r.p0) k_solve_levels(sp.view, r.l0, r.l1, r.p0, r.p1, true, vals, pis.pos, pis.val, pis.n, s);
                 k_solve_gate_level(sp.gate_view, r.g0, r.g1, vals, s, naf);
@@ -270,9 +301,12 @@ void Solve::run_levels() {
     const double per_entry = 32.0 * (kSolveCoefs - (sp.view.coef[kSolveQm] ? 1 : 2)) + 4 * 6 + 32 * 5;
     // an ECC entry reads its 128 bytes and up to four values; every variable it defines is a value written
     const uint64_t n_ecc_vars = sp.n_fixed + sp.n_var - (sp.n_gate - sp.n_range - sp.n_logic);
+    // a lookup entry reads its 16 bytes, three values, two offsets, and a row id and four columns of one
+    // table row (a bucket of one), and writes a value
     ctx->ktimer.end("solve_levels", s, e0,
-                    per_entry * (double)(sp.n_solved - sp.n_gate - n_ecc_vars) + 80.0 * (double)sp.n_gate +
-                        32.0 * (double)sp.n_two + 256.0 * (double)sp.n_ecc + 32.0 * (double)n_ecc_vars);
+                    per_entry * (double)(sp.n_solved - sp.n_gate - n_ecc_vars - sp.n_lookup) + 80.0 * (double)sp.n_gate +
+                        32.0 * (double)sp.n_two + 256.0 * (double)sp.n_ecc + 32.0 * (double)n_ecc_vars +
+                        (16 + 96 + 8 + 4 + 128 + 32) * (double)sp.n_lookup);
     tm.mark("solve_levels");
     ctx->ktimer.collect();
 }
@@ -290,9 +324,9 @@ void Solve::derive_outputs() {
 }  // namespace
 
 void load_solve_plan(pnp_ctx *ctx, const char *what, const uint32_t *input_ids, uint64_t n_inputs,
-                     const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, uint32_t ecc, int device_ptrs,
-                     pnp_solve_info *info) {
-    PlanBuild pb{ctx, what, n_inputs, n_outputs, gates, ecc, device_ptrs, info};
+                     const uint64_t *output_rows, uint64_t n_outputs, uint32_t gates, uint32_t ecc, uint32_t lookup,
+                     int device_ptrs, pnp_solve_info *info) {
+    PlanBuild pb{ctx, what, n_inputs, n_outputs, gates, ecc, lookup, device_ptrs, info};
     pb.preconditions();
     pb.mark_inputs(input_ids);
     pb.selector_rows();
@@ -320,6 +354,16 @@ void solve_ecc_entries(pnp_ctx *ctx, uint64_t out[2]) {
     }
     out[0] = sp.n_fixed;
     out[1] = sp.n_var;
+}
+
+void solve_lookup_entries(pnp_ctx *ctx, uint64_t out[2]) {
+    const SolvePlan &sp = ctx->key.solve;
+    if (!sp.loaded) {
+        set_error("no solve plan resident (pnp_load_solve_plan_lookup first)");
+        throw Error(PNP_E_NOKEY);
+    }
+    out[0] = sp.n_lookup;
+    out[1] = sp.n_indexed;
 }
 
 void solve_assignment(pnp_ctx *ctx, const uint64_t *inputs, uint64_t n_inputs, int device_ptrs,

@@ -44,6 +44,7 @@ SYMBOLS = ("gen_proof", "pnp_last_error", "pnp_ctx_create", "pnp_ctx_destroy",
            "pnp_load_solve_plan", "pnp_solved_public_inputs", "pnp_prove_solved", "pnp_check_solved",
            "pnp_load_solve_plan_gates", "pnp_solve_gate_entries",
            "pnp_load_solve_plan_ecc", "pnp_solve_ecc_entries",
+           "pnp_load_solve_plan_lookup", "pnp_solve_lookup_entries",
            "pnp_lde_blocks", "pnp_to_blocks", "pnp_intt_blocks", "pnp_t_combine_blocks", "pnp_t_combine_range")
 
 
@@ -353,6 +354,21 @@ class Context:
         var-add rows define) of the resident plan."""
         out = (C.c_uint64 * 2)()
         check(self.lib.pnp_solve_ecc_entries(self.h, C.byref(out)), "pnp_solve_ecc_entries")
+        return out[0], out[1]
+
+    def load_solve_plan_lookup(self, ids: int, n_inputs: int, rows: int, n_outputs: int, gates: int, ecc: int,
+                               lookup: int, device_ptrs: bool = False):
+        """pnp_load_solve_plan_lookup: load_solve_plan_ecc where, with `lookup`
+        = abi.SOLVE_LOOKUP, a q_lookup row defines its slot c from the key's
+        table.  Returns (rc, abi.SolveInfo) as load_solve_inputs."""
+        return self._load_solve("pnp_load_solve_plan_lookup", C.c_void_p(ids or None), n_inputs,
+                                C.c_void_p(rows or None), n_outputs, gates, ecc, lookup, int(device_ptrs))
+
+    def solve_lookup_entries(self):
+        """pnp_solve_lookup_entries: (variables lookup rows define, table rows
+        in the index) of the resident plan."""
+        out = (C.c_uint64 * 2)()
+        check(self.lib.pnp_solve_lookup_entries(self.h, C.byref(out)), "pnp_solve_lookup_entries")
         return out[0], out[1]
 
     def solved_public_inputs(self):

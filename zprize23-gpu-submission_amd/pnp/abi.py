@@ -181,8 +181,15 @@ class SolveInfo(C.Structure):
 #   pnp_load_solve_plan_ecc(ctx, input_ids, n_inputs, output_rows, n_outputs, gates, ecc, device_ptrs, info)
 #   pnp_solve_ecc_entries(ctx, out[2])
 SOLVE_RANGE, SOLVE_LOGIC = 1, 2
+# With lookup rows that define (lookup: SOLVE_LOOKUP):
+#   pnp_load_solve_plan_lookup(ctx, input_ids, n_inputs, output_rows, n_outputs, gates, ecc, lookup, device_ptrs, info)
+#   pnp_solve_lookup_entries(ctx, out[2])
 SOLVE_FIXED_ADD, SOLVE_VAR_ADD = 1, 2
+SOLVE_LOOKUP = 1
 SOLVE_ARGTYPES = {
+    "pnp_load_solve_plan_lookup": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, C.c_int, C.POINTER(SolveInfo)],
+    "pnp_solve_lookup_entries": [C.c_void_p, C.POINTER(C.c_uint64 * 2)],
     "pnp_load_solve_plan_ecc": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                 C.c_int, C.POINTER(SolveInfo)],
     "pnp_solve_ecc_entries": [C.c_void_p, C.POINTER(C.c_uint64 * 2)],
