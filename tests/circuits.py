@@ -188,11 +188,39 @@ class Composer:
         return GeneralInputs(self, n)
 
 
+def sigma_columns(cp: Composer, n: int, cycle_seed=None):
+    """The four sigma columns on the n-domain (canonical ints): cycles over the
+    slots of each variable, in slot order or, with cycle_seed, in a shuffle
+    seeded by it; rows past the gates keep the identity."""
+    lg = n.bit_length() - 1
+    w = fr_root(lg)
+    wp = [1] * n
+    for i in range(1, n):
+        wp[i] = wp[i - 1] * w % R_MOD
+    slots = {}
+    for i, (_, ws) in enumerate(cp.rows):
+        for j, v in enumerate(ws):
+            slots.setdefault(v, []).append((j, i))
+    sig = [[K_COSET[j] * wp[i] % R_MOD for i in range(n)] for j in range(4)]
+    if cycle_seed is not None:
+        srng = np.random.default_rng(cycle_seed)
+        slots = {v: [cyc[k] for k in srng.permutation(len(cyc))] for v, cyc in slots.items()}
+    for cyc in slots.values():
+        for k, (j, i) in enumerate(cyc):
+            j2, i2 = cyc[(k + 1) % len(cyc)]
+            sig[j][i] = K_COSET[j2] * wp[i2] % R_MOD
+    return sig
+
+
 class GeneralInputs:
     """Same interface as pnp_testlib.Inputs (arrays, circuit/pk/ck structs,
     oracle_proof, vk) for a Composer circuit."""
 
-    def __init__(self, cp: Composer, n: int):
+    def __init__(self, cp: Composer, n: int, cycle_seed=None):
+        """cycle_seed: the slots of each variable's cycle follow one another in
+        a shuffle seeded by it instead of in slot order.  Any cyclic order of
+        the same slot set is the same copy constraint; sigma is data to the
+        prover and the oracle alike."""
         lib = oracle()
         self.n = n
         self.lg_n = n.bit_length() - 1
@@ -200,23 +228,12 @@ class GeneralInputs:
         ng = len(cp.rows)
         self.n_gates = ng
         N8 = 8 * n
-        w = fr_root(lg)
-        wp = [pow(w, i, R_MOD) for i in range(n)]
         a = self.arrays = {}
         # witness (gate rows only; the prover pads with zeros)
         for j, name in enumerate(("w_l", "w_r", "w_o", "w_4")):
             a[name] = ints_to_arr([fr_mont(cp.vals[r[1][j]]) for r in cp.rows])
         a["q_lookup"] = ints_to_arr([fr_mont(r[0].get("q_lookup", 0)) for r in cp.rows])
-        # sigmas: cycles over the slots of each variable
-        slots = {}
-        for i, (_, ws) in enumerate(cp.rows):
-            for j, v in enumerate(ws):
-                slots.setdefault(v, []).append((j, i))
-        sig = [[K_COSET[j] * wp[i] % R_MOD for i in range(n)] for j in range(4)]
-        for cyc in slots.values():
-            for k, (j, i) in enumerate(cyc):
-                j2, i2 = cyc[(k + 1) % len(cyc)]
-                sig[j][i] = K_COSET[j2] * wp[i2] % R_MOD
+        sig = sigma_columns(cp, n, cycle_seed)
         polys = {name: [r[0].get(name, 0) % R_MOD for r in cp.rows] + [0] * (n - ng) for name in SEL}
         for j, name in enumerate(("left_sigma", "right_sigma", "out_sigma", "fourth_sigma")):
             polys[name] = sig[j]

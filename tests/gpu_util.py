@@ -24,3 +24,41 @@ def empty_dev(n_elems: int, limbs: int = 4):
     t = torch.zeros((n_elems, limbs), dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
     return t
+
+
+def proof_after_tables(ctx, prove, names):
+    """(proof, counters) of the proof that follows the context's table build:
+    a proof that finds the optional tables missing goes without them and has
+    them built in the background (context.h, "Deferred tables"); ctx.sync()
+    waits for that build, and the next proof, made with kernel timing on, uses
+    them.  prove(ctx) returns a ProofC; both proofs must be the same bytes."""
+    from pnp import abi
+    first = prove(ctx)
+    ctx.sync()
+    ctx.kernel_timing(True)
+    got = prove(ctx)
+    assert abi.proof_to_bytes(got) == abi.proof_to_bytes(first)
+    return got, {k: ctx.kernel_bytes(k) for k in names}
+
+
+def second_proof_counters(load, prove, names, after=None):
+    """proof_after_tables on a fresh context that load(ctx) gives its keys;
+    after(ctx, proof) runs before the context is closed."""
+    import pnp
+    ctx = pnp.Context(0)
+    try:
+        load(ctx)
+        got, c = proof_after_tables(ctx, prove, names)
+        if after is not None:
+            after(ctx, got)
+        return got, c
+    finally:
+        ctx.close()
+
+
+def host_keys(inp):
+    """load(ctx) for second_proof_counters: the instance's keys from host pointers."""
+    def load(ctx):
+        ctx.load_prover_key(inp.pk, inp.n, device_ptrs=False)
+        ctx.load_commit_key(inp.ck, inp.n, device_ptrs=False)
+    return load

@@ -114,21 +114,10 @@ def test_synth_merkle_matches_builder(pc, height):
 
 
 def _prove_v2_counters(inp, names, env=None):
-    import pnp
-    ctx = pnp.Context(0)
-    try:
-        ctx.load_prover_key(inp.pk, inp.n, device_ptrs=False)
-        ctx.load_commit_key(inp.ck, inp.n, device_ptrs=False)
-        # the first proof goes without the optional tables and builds them in
-        # the background (context.h); the second, after it, uses them
-        first = ctx.prove_ex(inp.circuit, False, pis_of(inp))
-        ctx.sync()
-        ctx.kernel_timing(True)
-        got = ctx.prove_ex(inp.circuit, False, pis_of(inp))
-        assert abi.proof_to_bytes(got) == abi.proof_to_bytes(first)
-        return got, {k: ctx.kernel_bytes(k) for k in names}
-    finally:
-        ctx.close()
+    # the first proof goes without the optional tables and builds them in
+    # the background (context.h); the second, after it, uses them
+    from gpu_util import host_keys, second_proof_counters
+    return second_proof_counters(host_keys(inp), lambda ctx: ctx.prove_ex(inp.circuit, False, pis_of(inp)), names)
 
 
 def test_merkle_wire_groups_used(pc):

@@ -64,6 +64,10 @@ struct pnp_ctx {
         int c = 0;                      // its window bits (msm_fold_c of one segment's n)
         uint64_t n = 0, total = 0, m = 0, len = 0;  // domain, bases, largest group count, MSM length
         uint64_t g[5] = {}, off[5] = {};
+        // what the build found per segment, for the counters (wires.hip
+        // credit_group_counts): groups before an ungrouped wire takes its n
+        // slots, and groups queued for a workgroup of their own
+        uint64_t found[5] = {}, heavy[5] = {};
         bool ident[5] = {};             // ungrouped wire: its scalars are its evaluations
         pnp::DevBuf grp[5], rep[5];     // row -> group slot, slot -> representative row
         pnp::DevBuf scal[5];            // per-proof group scalars at their slots (n each)

@@ -298,9 +298,10 @@ void build_wire_bases(pnp_ctx *ctx, uint64_t n) {
     uint32_t lg = 0;
     while ((1ULL << lg) < n) lg++;
     const uint64_t N = 4 * n;
-    DevBuf flag(16), tmp;
+    // bad, then the heavy-queue length of each segment (read back together)
+    DevBuf flag(32), tmp;
     uint32_t *bad = static_cast<uint32_t *>(flag.p);
-    PNP_HIP(hipMemsetAsync(bad, 0, 4, s));
+    PNP_HIP(hipMemsetAsync(bad, 0, 24, s));
     // the sigma evaluations this build reads, kept to recognise the key later
     wb.sigma.alloc(N * 32);
     for (int j = 0; j < 4; j++)
@@ -393,6 +394,7 @@ void build_wire_bases(pnp_ctx *ctx, uint64_t n) {
                                static_cast<const uint32_t *>(gstart.p), (uint64_t)g, n, C, bx[j].u64(), bad,
                                static_cast<const uint32_t *>(heavy.p));
             PNP_HIP(hipGetLastError());
+            PNP_HIP(hipMemcpyAsync(bad + 1 + j, heavy.p, 4, hipMemcpyDeviceToDevice, s));
             bg_step(s);
         };
         for (int j = 0; j < 4; j++) {
@@ -414,7 +416,7 @@ void build_wire_bases(pnp_ctx *ctx, uint64_t n) {
             uint32_t g = 0;
             PNP_HIP(hipMemcpyAsync(&g, gid_p + n - 1, 4, hipMemcpyDeviceToHost, s));
             PNP_HIP(hipStreamSynchronize(s));
-            wb.g[j] = g;
+            wb.g[j] = wb.found[j] = g;
             wb.ident[j] = (uint64_t)g * 10 > 9 * n;
             if (wb.ident[j]) {
                 wb.g[j] = n;
@@ -438,14 +440,16 @@ void build_wire_bases(pnp_ctx *ctx, uint64_t n) {
             uint32_t g = 0;
             PNP_HIP(hipMemcpyAsync(&g, gid_p + n - 1, 4, hipMemcpyDeviceToHost, s));
             PNP_HIP(hipStreamSynchronize(s));
-            wb.g[4] = g;
+            wb.g[4] = wb.found[4] = g;
             wb.ident[4] = (uint64_t)g * 10 > 9 * n;  // (not worth a segment: z commits from its evaluations)
             if (!wb.ident[4]) bases(4, g);
         }
     }
-    uint32_t hbad = 0;
-    PNP_HIP(hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, s));
+    uint32_t hflag[6] = {};
+    PNP_HIP(hipMemcpyAsync(hflag, bad, sizeof hflag, hipMemcpyDeviceToHost, s));
     PNP_HIP(hipStreamSynchronize(s));
+    const uint32_t hbad = hflag[0];
+    for (int j = 0; j < 5; j++) wb.heavy[j] = hflag[1 + j];
     // the wires are worth their segments only when some wire has far fewer
     // groups than rows; z when its runs merge >= 10% of the rows
     bool gain = false;
@@ -555,6 +559,22 @@ bool wire_bases_ready(pnp_ctx *ctx, uint64_t n) {
     return wb.ok;
 }
 
+// a timed proof on a context whose groups are built: what the build found,
+// per segment, whether or not this proof commits over them
+void credit_group_counts(pnp_ctx *ctx, uint64_t n) {
+    if (!ctx->ktimer.enabled || tables_busy(ctx)) return;
+    const auto &wb = ctx->wb;
+    if (!wb.built || wb.n != n || wb.pk_gen != ctx->key.gen || !wb.sigma.p) return;
+    static const char *const found[5] = {"groups_found_a", "groups_found_b", "groups_found_c", "groups_found_d",
+                                         "groups_found_z"};
+    static const char *const heavy[5] = {"groups_heavy_a", "groups_heavy_b", "groups_heavy_c", "groups_heavy_d",
+                                         "groups_heavy_z"};
+    for (int j = 0; j < 5; j++) {
+        ctx->ktimer.credit(found[j], (double)wb.found[j]);
+        ctx->ktimer.credit(heavy[j], (double)wb.heavy[j]);
+    }
+}
+
 }  // namespace
 
 void wire_bases_reset(pnp_ctx *ctx) { ctx->wb = pnp_ctx::WireBases{}; }
@@ -564,9 +584,10 @@ void wire_bases_build(pnp_ctx *ctx, uint64_t n) {
 bool wire_groups_enabled() { return groups_enabled(); }
 
 bool commit_wires_grouped(pnp_ctx *ctx, const uint64_t *const *d_evals, uint64_t n, CommitmentC *const *out) {
-    if (!groups_enabled() || ctx->hbm_groups_off || !lagrange_table(ctx, n) || !wire_bases_ready(ctx, n) ||
-        !ctx->wb.wires_ok)
-        return false;
+    if (!groups_enabled() || ctx->hbm_groups_off || !lagrange_table(ctx, n)) return false;
+    const bool ready = wire_bases_ready(ctx, n);
+    credit_group_counts(ctx, n);
+    if (!ready || !ctx->wb.wires_ok) return false;
     auto &wb = ctx->wb;
     hipStream_t s = ctx->stream;
     uint32_t *flag = static_cast<uint32_t *>(wb.flag.p);
